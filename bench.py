@@ -18,11 +18,20 @@ _advect phase, 4096 points), elasticity2Dstretch (one _solve_deformation phase, 
 points), elasticity3Dbunny (SIREN 5x256, 64^3 points); a step is one iteration of every
 phase of that model's timestep.
 
-Also reported: a roofline object for the dominant kernel (HIP events on its launch
-stream, eager re-run of the same step after the timed region) and a CPU baseline
-(the oracle restatement of the reference's torch graph, timed on this host).
+A plain run sets up, warms up, times the K steps and prints the result line.  With --full the
+line also carries a roofline object for the dominant kernel (HIP events on its launch
+stream, eager re-run of the same step after the timed region), the `plain` line (the
+reference's unchanged phase bodies, --plain-line) and a CPU baseline (the oracle restatement
+of the reference's torch graph, timed on this host).
+
+--dump-outputs DIR writes what the last timed step left its caller as DIR/<name>.npy (float32):
+each phase's loss dict of its last iteration (loss.<phase>.<key>) and every trainable
+network's parameters after it (net.<network>.<parameter>).  With it the sustained warm-up is a
+fixed number of timesteps instead of --warm-ms of wall time, so the run executes the same
+iterations (same seeds, same device sampler stream) every time.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling auto|strong|weak] [--config NAME]
+                       [--full] [--dump-outputs DIR]
   N > 1: one rank per GPU over RCCL.  Under torch.distributed.run (WORLD_SIZE set) the ranks
   are the launcher's; otherwise bench.py starts `python -m torch.distributed.run
   --nproc-per-node N` itself as a child process (before any GPU call) and exits with its code.
@@ -50,6 +59,7 @@ PRECISION = {"fp32": ("fp32", 6, 3), "bf16x3": ("bf16x3", 3, 2), "bf16": ("bf16"
              # dominant launch is a backward: its products and kernel names are the bf16 ones)
              "mixed": ("bf16x3/bf16", 1, 1)}
 HBM_PEAK_GBS = 8000.0
+DUMP_WARM_TIMESTEPS = 128  # --dump-outputs: sustained warm-up timesteps (the headline's ~200 ms of replays)
 
 
 T0 = time.time()
@@ -67,6 +77,15 @@ def parse():
     ap.add_argument("--config", default="fluid2Dtlgn", choices=sorted(WORKLOADS),
                     help="BASELINE.json workload (default: configs[1], the headline)")
     ap.add_argument("--scaling", choices=["auto", "strong", "weak"], default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own and add them to the "
+                         "line: the roofline object (--no-roofline), the `plain` line (--plain-line) and the CPU "
+                         "baseline (--no-cpu-baseline, --cpu-seconds); without it none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left its caller as DIR/<name>.npy (float32): "
+                         "every phase's last loss dict and every trainable network's parameters; the sustained "
+                         "warm-up is then a fixed number of timesteps (--warm-ms is not used), so equal arguments "
+                         "run equal iterations")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--precision", choices=sorted(PRECISION), default="fp32",
                     help="matrix-core precision of every jet: fp32 (fp32-accurate split-bf16, the parity "
@@ -77,7 +96,7 @@ def parse():
                          "bodies written only against the reference's base API (separate band samplers, torch "
                          "residuals and energies, lowered by the loop: base/lower.py) -- the drop-in case")
     ap.add_argument("--plain-line", choices=["auto", "on", "off"], default="auto",
-                    help="also time the unchanged reference phase bodies (--api plain) after the fused run and add "
+                    help="--full: also time the unchanged reference phase bodies (--api plain) after the fused run and add "
                          "them to the line as `plain` (auto: on for the default fluid2Dtlgn line on one GPU)")
     ap.add_argument("--shard-of", type=int, default=1,
                     help="one process runs the per-rank shard of a K-rank strong-scaling run (global batch / K "
@@ -94,9 +113,9 @@ def parse():
                     help="x6 backward products on the fp16 matrix cores, INSR_BWD_F16_* mask (A/B studies; "
                          "-1 = library default)")
     ap.add_argument("--lib", default=None, help="an alternative build of libinsr_hip.so (same-box A/B studies only)")
-    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="--full: budget of the CPU-baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline object")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL) or gloo (functional rehearsal)")
     ap.add_argument("--dp-path", action="store_true",
                     help="one process runs the data-parallel iteration itself (gradient arena, a world-1 RCCL "
@@ -303,9 +322,11 @@ def run_timestep(model, wl, loops, i0, k):
     with the prev-net snapshots between them.  (The per-phase optimiser reset of the reference's
     loop is an O(1) cost per phase loop of max_n_iters iterations; the phase loops here keep
     their optimiser and hipGraphs across bench timesteps.)"""
+    outs = []
     for p, pl in enumerate(loops):
         snapshot(model, wl, p)
-        pl.run_iters(i0, k)  # groups of insr_graph_unroll iterations per graph replay
+        outs.append(pl.run_iters(i0, k))  # groups of insr_graph_unroll iterations per graph replay
+    return outs  # each phase's device loss dict of its last iteration (no host read here)
 
 
 def sync_all(world):
@@ -685,11 +706,16 @@ def measure(args, model, wl, world):
     # sustained untimed timesteps (the graphs replayed as in the timed region) until --warm-ms of wall
     # time has passed: the timed region then starts with the replays warm and the device clocks at their
     # sustained level (without it the first timed timesteps run slower, profiles/r05/warm/)
+    # (--dump-outputs: DUMP_WARM_TIMESTEPS of them instead, whatever the clock says -- the device sampler's
+    # stream and the networks then stand at the same iteration in every run with these arguments)
     k_warm = U if (U > 1 and not args.no_graph) else 1
     t_warm = time.perf_counter()
-    while (time.perf_counter() - t_warm) * 1e3 < args.warm_ms:
+    n_warm = 0
+    while (n_warm < DUMP_WARM_TIMESTEPS) if args.dump_outputs else \
+            ((time.perf_counter() - t_warm) * 1e3 < args.warm_ms):
         run_timestep(model, wl, loops, w_eff, k_warm)
         w_eff += k_warm
+        n_warm += 1
         torch.cuda.synchronize()
     # timed region: --steps iterations of every phase, as `nts` timesteps in step() order
     # (K iterations per phase, phases in order, median of 5 timesteps); no loss
@@ -703,8 +729,9 @@ def measure(args, model, wl, world):
     t0 = time.perf_counter()
     evs[0].record()
     i = w_eff
+    last = None
     for t, k in enumerate(ks):
-        run_timestep(model, wl, loops, i, k)
+        last = run_timestep(model, wl, loops, i, k)
         evs[t + 1].record()
         i += k
     sync_all(world)
@@ -718,7 +745,25 @@ def measure(args, model, wl, world):
     for pl in loops:  # which replay form each phase loop ended up with
         log(f"  {pl.tag}: graph {pl.graph is not None}, unroll {pl.unroll}, group graph {pl.graphU is not None}"
             + (f", capture error {pl.capture_error}" if getattr(pl, "capture_error", None) else ""))
-    return loops, elapsed, ts_ms, ks, w_eff
+    return loops, elapsed, ts_ms, ks, w_eff, last
+
+
+def dump_outputs(path, model, wl, last):
+    """--dump-outputs: what the last timed step handed its caller, one float32 .npy per array -- every
+    phase's loss dict of its last iteration (the return value of PhaseLoop.run_iters) and every trainable
+    network's parameters after it (the tensors save_ckpt writes).  A few MB at most (SIREN 5x256: 1.3 MB)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, losses in zip(wl["phases"], last):
+        for key, v in losses.items():
+            arrays[f"loss.{name.lstrip('_')}.{key}"] = v
+    for key, net in model._trainable_networks.items():
+        for pname, v in net.state_dict().items():
+            arrays[f"net.{key}.{pname}"] = v
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v.detach().to(torch.float32).cpu().numpy())
+    return sorted(arrays)
 
 
 def main():
@@ -734,7 +779,10 @@ def main():
     bwd_f16 = _native.bwd_f16_mask()  # the backward products on fp16 matrix cores in effect
     nph = len(wl["phases"])
     log(f"model built, {n_local} points per rank per phase")
-    loops, elapsed, ts_ms, ks, w_eff = measure(args, model, wl, world)
+    loops, elapsed, ts_ms, ks, w_eff, last = measure(args, model, wl, world)
+    if args.dump_outputs and rank == 0:  # (every rank holds the same networks)
+        names = dump_outputs(args.dump_outputs, model, wl, last)
+        log(f"wrote {len(names)} arrays to {args.dump_outputs}")
     nts = len(ks)
     # points all ranks processed: strong = the global batch, weak = world x the per-rank batch
     n_all = interior_points(cfg, wl) if (args.scaling == "strong" and args.shard_of == 1) else n_local * world
@@ -752,7 +800,9 @@ def main():
                    "points_per_phase_iter": n_all, "phases": nph, "global_batch": n_all,
                    "seq_len": None, "parallelism": f"dp{world}", "graph": not args.no_graph,
                    "precision": args.precision, "api": args.api, "sync_every": cfg.insr_sync_every,
-                   "graph_unroll": 1 if args.no_graph else max(1, args.graph_unroll), "warm_ms": args.warm_ms,
+                   "graph_unroll": 1 if args.no_graph else max(1, args.graph_unroll),
+                   "warm_ms": None if args.dump_outputs else args.warm_ms,
+                   "warm_timesteps": DUMP_WARM_TIMESTEPS if args.dump_outputs else None, "full": args.full,
                    "jet_precision": jet_precision_names(args.precision),
                    "bwd_policy": args.bwd_policy, "shard_of": args.shard_of, "dp_path": args.dp_path,
                    "seeds_in_bwd": bool(getattr(cfg, "insr_seed_in_bwd", True)),
@@ -769,20 +819,22 @@ def main():
         "process_group": {"backend": args.backend if (world > 1 or args.dp_path) else None, "world_size": world,
                           "rank_devices": args.rank_devices},
     }
-    if not args.no_roofline:  # every rank runs the eager steps (they contain the all-reduce)
+    # --full: the legs below take runs of their own (a plain run ends with the line above)
+    if args.full and not args.no_roofline:  # every rank runs the eager steps (they contain the all-reduce)
         roof = roofline(loops, n_local, args.precision)
         if rank == 0:
             result["roofline"] = roof
         log("roofline done")
     plain_on = args.plain_line == "on" or (args.plain_line == "auto" and args.config == "fluid2Dtlgn")
-    if plain_on and world == 1 and args.api == "fused" and args.shard_of == 1:
+    if args.full and plain_on and world == 1 and args.api == "fused" and args.shard_of == 1:
         # the drop-in number, driver-timed: the reference's phase bodies as written (pde/*_plain.py) on the
         # same kernels, through the loop's lowering and deferred jets, same steps / warm-up / timing
         pargs = argparse.Namespace(**vars(args))
         pargs.api = "plain"
         pmodel, _, _, _ = build_model(pargs, world, rank)
         log("plain model built")
-        _, p_el, p_ts, p_ks, _ = measure(pargs, pmodel, wl, world)
+        pargs.dump_outputs = None  # nothing of it is dumped: it warms up for --warm-ms as in any other run
+        _, p_el, p_ts, p_ks, _, _ = measure(pargs, pmodel, wl, world)
         p_val = n_all * nph * args.steps / p_el
         p_per_ts = sorted((n_all * nph * k) / (ms * 1e-3) for k, ms in zip(p_ks, p_ts))
         result["plain"] = {"value": round(p_val, 1), "ms_per_step": round(p_el / args.steps * 1e3, 4),
@@ -791,7 +843,7 @@ def main():
                            "model": f"pde/{wl['pde']}_plain.py: the reference's phase bodies as written "
                                     "(reference base API only; base/lower.py lowers them)"}
         log(f"plain line {p_val / 1e6:.1f} M pts/s")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.config, args.cpu_seconds)
         log("cpu baseline done")
         result["speedup_vs_cpu_baseline"] = round(value / result["cpu_baseline"]["value"], 1)

@@ -27,3 +27,37 @@ def test_scaling_defaults():
     sys.path.insert(0, ROOT)
     import bench
     assert set(bench.STRONG_CONFIGS) == {"elasticity3Dbunny", "fluid2DtlgnM"}
+
+
+def test_plain_run_options(monkeypatch):
+    """--full and --dump-outputs are off in a plain run (the legs beside the timed steps run only with --full)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    """dump_outputs(): one float32 .npy per array of the last timed step -- every phase's loss dict and every
+    trainable network's state_dict -- under names that say which."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Model:
+        _trainable_networks = {"field": torch.nn.Linear(3, 2).double()}
+
+    last = [{"main": torch.tensor(1.5), "bc": torch.tensor(0.25, dtype=torch.float64)}]
+    names = bench.dump_outputs(str(tmp_path / "d"), Model(), {"phases": ("_advect",)}, last)
+    assert names == ["loss.advect.bc", "loss.advect.main", "net.field.bias", "net.field.weight"]
+    assert sorted(os.listdir(tmp_path / "d")) == [n + ".npy" for n in names]
+    got = {n: np.load(tmp_path / "d" / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert float(got["loss.advect.main"]) == 1.5 and float(got["loss.advect.bc"]) == 0.25
+    w = Model._trainable_networks["field"].weight.detach().to(torch.float32).numpy()
+    assert got["net.field.weight"].shape == (2, 3) and np.array_equal(got["net.field.weight"], w)

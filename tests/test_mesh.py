@@ -1,7 +1,7 @@
 """Mesh input (pde/mesh.py; the reference's meshio + torchgp path, elasticity/model.py:75-93,
 198-207, elasticity/torchgp/*.py).  CPU tests: a MEDIT cube written here (exact volumes,
-faces and sample moments), and -- when /root/reference is present (build container only)
--- the reference's own bunny.mesh, whose file carries the surface triangles that
+faces and sample moments), and the reference's own bunny.mesh (its blocks, stored under
+tests/golden/ and written back as a MEDIT file), whose file carries the surface triangles that
 boundary_faces() must reproduce from the tets.  Sampling parity is distributional (the
 reference draws with numpy / torch.distributions): checked by exact containment and
 moment tests."""
@@ -151,11 +151,24 @@ def test_elasticity_model_mesh_phase(cube):
     assert abs(float(ld["main"]) - float(ref)) <= 1e-5 * abs(float(ref)) + 1e-6
 
 
-REF_BUNNY = "/root/reference/elasticity/data/bunny.mesh"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+BUNNY_NPZ = os.path.join(GOLDEN, "bunny_mesh.npz")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BUNNY), reason="reference tree not mounted")
-def test_reference_bunny_mesh():
+@pytest.fixture(scope="module")
+def ref_bunny(tmp_path_factory):
+    """The reference's bunny.mesh as a MEDIT file again: its vertices (float64 as read, written with 17
+    digits: the same doubles), tetrahedra and surface triangles, kept as data under tests/golden/
+    (make_bunny_fixture.py)."""
+    with np.load(BUNNY_NPZ) as z, np.load(os.path.join(GOLDEN, "bunny_faces.npz")) as zf:
+        V, T, F = z["V"], z["T"], zf["F"]
+    p = str(tmp_path_factory.mktemp("bunny") / "bunny.mesh")
+    write_medit(p, V, T, F)
+    return p
+
+
+def test_reference_bunny_mesh(ref_bunny):
+    REF_BUNNY = ref_bunny
     V, blocks = M.read_medit(REF_BUNNY)
     T, F = blocks["Tetrahedra"], blocks["Triangles"]
     assert V.shape == (18592, 3) and T.shape == (76854, 4) and F.shape == (20522, 3)
@@ -170,19 +183,14 @@ def test_reference_bunny_mesh():
     assert abs(float(Vn.norm(dim=1).max()) - 2.0) < 1e-5
 
 
-BUNNY_NPZ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bunny_mesh.npz")
-
-
-def test_bunny_fixture_loads_like_the_reference_mesh():
+def test_bunny_fixture_loads_like_the_reference_mesh(ref_bunny):
     """The derived fixture (tests/golden/make_bunny_fixture.py) is what the elasticity3Dbunny
     bench trains on: same vertex / tet counts as the reference's bunny.mesh, positive tet
-    volumes, normalised radius 2, and -- where the reference tree is mounted -- the same
-    loaded arrays as reading the .mesh itself."""
+    volumes, normalised radius 2, and the same loaded arrays as reading the .mesh itself."""
     Vn, E, SF = M.load_mesh(BUNNY_NPZ, 3)
     assert Vn.shape == (18592, 3) and E.shape == (76854, 4) and SF.shape == (20522, 3)
     assert abs(float(Vn.norm(dim=1).max()) - 2.0) < 1e-5
     vol = M.tet_volumes(Vn.double(), torch.as_tensor(E))
     assert bool(torch.all(vol > 0))
-    if os.path.exists(REF_BUNNY):
-        Vr, Er, SFr = M.load_mesh(REF_BUNNY, 3)
-        assert torch.equal(Vn, Vr) and np.array_equal(E, Er) and np.array_equal(SF, SFr)
+    Vr, Er, SFr = M.load_mesh(ref_bunny, 3)
+    assert torch.equal(Vn, Vr) and np.array_equal(E, Er) and np.array_equal(SF, SFr)

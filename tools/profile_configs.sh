@@ -8,4 +8,4 @@ export TMPDIR=/tmp
 timeout -k 10 300 python -u -m pytest tests -q -m gpu -x --timeout 120 --timeout-method thread -k "elastic or el3d or phases" > $O/tests.log 2>&1 || exit $?
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $PWD/$O/prof_el2d -o run --output-format csv -- python bench.py --config elasticity2Dstretch --steps 10 --warmup 3 --no-cpu-baseline --no-roofline > $O/prof_el2d.log 2>&1 || exit $?
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $PWD/$O/prof_el3d -o run --output-format csv -- python bench.py --config elasticity3Dbunny --steps 5 --warmup 3 --no-cpu-baseline --no-roofline > $O/prof_el3d.log 2>&1 || exit $?
-timeout -k 10 300 python bench.py --config elasticity2Dstretch --steps 20 --warmup 3 --cpu-seconds 10 > $O/bench_el2d.log 2>&1 || exit $?
+timeout -k 10 300 python bench.py --full --config elasticity2Dstretch --steps 20 --warmup 3 --cpu-seconds 10 > $O/bench_el2d.log 2>&1 || exit $?
