@@ -128,6 +128,11 @@ int insr_siren_wsplit(float* params, int d_in, int d_out, int num_hidden, int wi
  * exact).  Returns INSR_ERANGE when flagged, 0 when not (waits for `stream`; a host sync point).
  * insr_siren_wsplit clears the flag; the Adam launches only set it. */
 int insr_siren_wsplit_status(const float* params, int d_in, int d_out, int num_hidden, int width, void* stream);
+/* Probe of the fp16 two-term split every f16x3 plane goes through (weights and streams alike): pair i,
+ * (in[2 i], in[2 i + 1]), gives the packed words hi[i] = (fp16(a), fp16(b)) and lo[i] = (fp16(a - hi_a),
+ * fp16(b - hi_b)), round to nearest even, first value in the low half.  No scale, no range guard: the
+ * callers' business.  For tests of the split itself. */
+int insr_split_f16(const float* in, unsigned* hi, unsigned* lo, long n_pairs, void* stream);
 
 /* 1 if (d_in, d_out, width, mode) is served by a compiled kernel, else 0. */
 int insr_siren_supported(int d_in, int d_out, int num_hidden, int width, int mode);

@@ -175,6 +175,7 @@ SIGNATURES = {
     "insr_siren_wsplit_floats": (_L, [_I, _I]),
     "insr_siren_wsplit": (_I, [_P, _I, _I, _I, _I, _P]),
     "insr_siren_wsplit_status": (_I, [_P, _I, _I, _I, _I, _P]),
+    "insr_split_f16": (_I, [_P, _P, _P, _L, _P]),
     "insr_siren_jet_fwd_mixed": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "insr_adam_step_nets": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _I, _P]),
     "insr_adam_plateau_step_nets": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _I, _P]),

@@ -647,6 +647,11 @@ int insr_siren_wsplit(float* params, int din, int dout, int L, int W, void* stre
   return wsplit_launch(params, din, dout, L, W, params + wsplit_offset(din, dout, L, W), (hipStream_t)stream);
 }
 
+int insr_split_f16(const float* in, unsigned* hi, unsigned* lo, long npairs, void* stream) {
+  if (npairs < 0 || npairs > (1L << 31) || (npairs && (!in || !hi || !lo))) return INSR_EINVAL;
+  return split_f16_probe_launch(in, hi, lo, npairs, (hipStream_t)stream);
+}
+
 // A call without INSR_MODE_WSPLIT whose kernels read weight planes: a per-(device, stream,
 // slot) scratch [copy of the parameters | planes] is filled (one copy + one split launch) and
 // used as the params buffer.  Allocation happens outside stream capture only.

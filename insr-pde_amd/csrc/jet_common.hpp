@@ -126,6 +126,21 @@ __device__ __forceinline__ float sum16(float v) {
   return v;
 }
 
+// four such sums at once, step by step: the four DPP chains interleave, each step's operands two
+// instructions old when the next one reads them (no wait states between dependent DPP reads); every
+// element's additions are sum16's, in its order
+__device__ __forceinline__ floatx4 sum16x4(floatx4 v) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = add_dpp<0xB1>(v[r]);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = add_dpp<0x4E>(v[r]);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = add_dpp<0x141>(v[r]);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = add_dpp<0x140>(v[r]);
+  return v;
+}
+
 // ---------------------------------------------------------------------------
 // sin / cos of w*z.  Two-part Cody-Waite reduction by 2 pi (n = rint(x / 2 pi); 6.28125 n is
 // exact for |n| < 2^16) to r in [-pi, pi], then the hardware v_sin_f32 / v_cos_f32 on
@@ -157,25 +172,56 @@ __device__ __forceinline__ bool wave_any_big(float amax) {
   return __any(amax > kFastArgMax);
 }
 
+// Maxima of NON-NEGATIVE floats (no NaN) across lanes, on their bit patterns: such floats order like
+// unsigned integers, and the integer maximum needs no canonicalising pass over its operands and fuses
+// with the DPP read (one v_max_u32_dpp per step).  max(keep, the lane CTRL selects' give):
 template <int CTRL>
-__device__ __forceinline__ float max_dpp(float v) {
-  const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false);
-  return fmaxf(v, __builtin_bit_cast(float, o));
+__device__ __forceinline__ unsigned umax_dpp(unsigned keep, unsigned give) {
+  const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)give, CTRL, 0xF, 0xF, true);
+  return keep > o ? keep : o;
 }
-// max over the wave's 64 lanes of NON-NEGATIVE values as a wave-uniform (scalar) result: the max of
-// each 16-lane row by four DPP steps (as sum16), then the four rows' maxima read into scalars and
-// combined as unsigned integers (non-negative floats order like their bit patterns) -- no LDS
-// crossbar round trips (__shfl_xor's ds_bpermute chain)
-__device__ __forceinline__ float wave_max_nn(float v) {
-  v = max_dpp<0xB1>(v);
-  v = max_dpp<0x4E>(v);
-  v = max_dpp<0x141>(v);
-  v = max_dpp<0x140>(v);
-  const int b = __builtin_bit_cast(int, v);
-  const unsigned r0 = (unsigned)__builtin_amdgcn_readlane(b, 0), r1 = (unsigned)__builtin_amdgcn_readlane(b, 16);
-  const unsigned r2 = (unsigned)__builtin_amdgcn_readlane(b, 32), r3 = (unsigned)__builtin_amdgcn_readlane(b, 48);
-  const unsigned m01 = r0 > r1 ? r0 : r1, m23 = r2 > r3 ? r2 : r3;
-  return __builtin_bit_cast(float, m01 > m23 ? m01 : m23);
+// the four 16-lane rows combined (every lane: the max over the lanes of its column): the odd rows
+// swapped with the even ones, then the upper half of the wave with the lower (gfx950 lane swaps)
+__device__ __forceinline__ unsigned umax_rows(unsigned v) {
+  const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+  v = r[0] > r[1] ? r[0] : r[1];
+  const auto q = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  return q[0] > q[1] ? q[0] : q[1];
+}
+// Wave maxima of NC (<= 5) classes at once: lane l < NC gets class l's maximum over the 64 lanes.  The
+// first two steps (lane ^ 1, lane ^ 2) are a reduce-scatter: each lane of a pair keeps one of two classes
+// and hands the other to its partner, so classes 0..3 shrink to ONE register holding class lane & 3,
+// which the quad rotations (row_ror 4, 8) and the row swaps then finish; class 4 rides in a second one.
+// 28 VALU operations for 5 classes, none scalar (one register per class: 4 DPP steps, 4 scalar read-backs
+// and 3 scalar maxima each)
+template <int NC>
+__device__ __forceinline__ unsigned wave_umax_classes(const unsigned (&u)[5], int lane) {
+  unsigned r;
+  if constexpr (NC > 1) {
+    const bool b0 = lane & 1, b1 = lane & 2;
+    const unsigned r01 = umax_dpp<0xB1>(b0 ? u[1] : u[0], b0 ? u[0] : u[1]);
+    if constexpr (NC > 2) {
+      const unsigned r23 = umax_dpp<0xB1>(b0 ? u[3] : u[2], b0 ? u[2] : u[3]);
+      r = umax_dpp<0x4E>(b1 ? r23 : r01, b1 ? r01 : r23);
+    } else {
+      r = umax_dpp<0x4E>(r01, r01);
+    }
+  } else {
+    r = umax_dpp<0xB1>(u[0], u[0]);
+    r = umax_dpp<0x4E>(r, r);
+  }
+  r = umax_dpp<0x124>(r, r);
+  r = umax_dpp<0x128>(r, r);
+  r = umax_rows(r);
+  if constexpr (NC > 4) {
+    unsigned q = umax_dpp<0xB1>(u[4], u[4]);
+    q = umax_dpp<0x4E>(q, q);
+    q = umax_dpp<0x124>(q, q);
+    q = umax_dpp<0x128>(q, q);
+    q = umax_rows(q);
+    r = lane == 4 ? q : r;
+  }
+  return r;
 }
 
 // max over the wave's 64 lanes (every lane gets it)
@@ -627,6 +673,7 @@ int dispatch_fwd_mixed_q(int NT, int din, const InsrJetJob* jobs, const int* mod
 // the pre-split weight planes of (prm, shape) written to `planes` (wsplit_offset floats after prm
 // in a params buffer of INSR_MODE_WSPLIT), one launch
 int wsplit_launch(const float* prm, int din, int dout, int L, int W, float* planes, hipStream_t st);
+int split_f16_probe_launch(const float* in, unsigned* hi, unsigned* lo, long npairs, hipStream_t st);
 void wide_launch_threads(long n, int din, int dout, int L, int W, int S, long* out);
 // resident-dW backward (jet_x6r.hpp: W = 128, L <= 4, split-bf16 x6): one persistent launch + the
 // fixed-order partial sums

@@ -74,6 +74,7 @@ struct FbGeo {
   static constexpr size_t SW_OFF = P_BYTES + H_BYTES + ZS_BYTES;
   static constexpr size_t SACC_OFF = SW_OFF + (size_t)SW_FLOATS * 4;
   static constexpr size_t SEED_OFF = SACC_OFF + (size_t)kFbSmallMax * 4;
+  static_assert(SACC_OFF % 16 == 0, "the compact row's b128 updates (bias and output-layer sums)");
   static constexpr size_t MX_OFF = SEED_OFF + (size_t)S * 3 * 16 * 4;
   // in-kernel seeds (saved-stream variant): the adjoints of the block's tiles [tile][S][3][16] (at most
   // kFbSeedTiles tiles per block), then the waves' square sums [8][INSR_SEED_MAX]
@@ -305,24 +306,25 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
     float* seed = reinterpret_cast<float*>(lbt + GG::SEED_OFF);
     float* mx = reinterpret_cast<float*>(lbt + GG::MX_OFF);
     // block maxima of NC (<= 5) classes of non-negative values: each wave's values in, the block's out
-    // (wave-uniform); one barrier.  Slot [class][wave], two slots alternate (each exchange has a barrier)
+    // (wave-uniform); one barrier.  Slot [class][wave], two slots alternate (each exchange has a barrier).
+    // Before the barrier lane l < NC gets its wave's maximum of class l (wave_umax_classes: all classes
+    // in one packed reduction) and stores it; after it every lane folds the 8 waves' entries of each
+    // class.  All on the bit patterns: non-negative floats order like unsigned integers
     auto exchange = [&](float (&m)[5], auto ncls) __attribute__((always_inline)) {
       constexpr int NC = decltype(ncls)::value;
+      unsigned* mxu = reinterpret_cast<unsigned*>(mx);
+      unsigned u[5];
 #pragma unroll
-      for (int k = 0; k < NC; ++k) m[k] = wave_max_nn(m[k]);
-      if (lane < NC) {
-        float v = m[0];
-#pragma unroll
-        for (int k = 1; k < NC; ++k) v = lane == k ? m[k] : v;
-        mx[(slot * 5 + lane) * 8 + wave] = v;
-      }
+      for (int k = 0; k < 5; ++k) u[k] = k < NC ? __builtin_bit_cast(unsigned, m[k]) : 0u;
+      const unsigned w = wave_umax_classes<NC>(u, lane);
+      if (lane < NC) mxu[(slot * 5 + lane) * 8 + wave] = w;
       __syncthreads();
 #pragma unroll
       for (int k = 0; k < NC; ++k) {
-        const floatx4 a = *reinterpret_cast<const floatx4*>(mx + (slot * 5 + k) * 8);
-        const floatx4 b = *reinterpret_cast<const floatx4*>(mx + (slot * 5 + k) * 8 + 4);
-        const float v = fmaxf(fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3])), fmaxf(fmaxf(b[0], b[1]), fmaxf(b[2], b[3])));
-        m[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+        const u32x4 a = *reinterpret_cast<const u32x4*>(mxu + (slot * 5 + k) * 8);
+        const u32x4 b = *reinterpret_cast<const u32x4*>(mxu + (slot * 5 + k) * 8 + 4);
+        const unsigned v = max(max(max(a[0], a[1]), max(a[2], a[3])), max(max(b[0], b[1]), max(b[2], b[3])));
+        m[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)v));
       }
       slot ^= 1;
     };
@@ -474,16 +476,21 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
     }  // forward (recompute only)
 
     // ---------------- reverse ----------------
-    // output layer (exact fp32 VALU): hb = W_out^T g, dW_out / db_out into the compact row
-    floatx4 zc[S];  // z-streams of the current layer
-    if constexpr (SAVED) {
-      zload(L, zc);
-    } else {
+    // z-streams and sin / cos of the current layer and of the one below it: two sets that swap roles
+    // from layer to layer (compile-time naming through the unrolled bwd_layer calls) instead of a copy,
+    // so layer j - 1's sin / cos -- computed once, for its h planes -- are its sine reverse's too
+    floatx4 zq[2][S], snq[2], csq[2];
+    {
+      floatx4(&zc)[S] = zq[0];
+      if constexpr (SAVED) {
+        zload(L, zc);
+      } else {
 #pragma unroll
-      for (int s = 0; s < S; ++s) zc[s] = zr[ZR - 1][s];
+        for (int s = 0; s < S; ++s) zc[s] = zr[ZR - 1][s];
+      }
+      fb_sincos(zc[0], snq[0], csq[0]);
     }
-    floatx4 sn, cs;
-    fb_sincos(zc[0], sn, cs);
+    // output layer (exact fp32 VALU): hb = W_out^T g, dW_out / db_out into the compact row
     floatx4 hb[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) hb[s] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -502,18 +509,15 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
       floatx4 acc4 = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < S; ++s) {
-        const floatx4 hs = fb_h<S, LAP>(s, zc, sn, cs);
+        const floatx4 hs = fb_h<S, LAP>(s, zq[0], snq[0], csq[0]);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           acc4[r] = fmaf(ga[s], hs[r], acc4[r]);
           hb[s][r] = fmaf(w4[r], ga[s], hb[s][r]);
         }
       }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = sum16(acc4[r]);
-        if (c == 0) sacc[so + (long)o * W + n0 + r] += v;
-      }
+      acc4 = sum16x4(acc4);
+      if (c == 0) *reinterpret_cast<floatx4*>(sacc + so + (long)o * W + n0) += acc4;
       if (wave == 0) {
         const float v = sum16(g == 0 ? ga[0] : 0.f);
         if (lane == 0) sacc[so + (long)dout * W + o] += v;
@@ -525,15 +529,18 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
       constexpr int j = decltype(jc)::value;
       constexpr int sp = 11 + 5 * (L - j);
       const u32x4* wsl = wsp;
+      constexpr int qc = (L - j) & 1;  // this layer's set; the other one becomes layer j - 1's
+      floatx4(&zc)[S] = zq[qc];
+      floatx4(&zp)[S] = zq[qc ^ 1];
+      const floatx4 &sn = snq[qc], &cs = csq[qc];
+      floatx4 &snp = snq[qc ^ 1], &csp = csq[qc ^ 1];
       // z-streams of layer j - 1 (layer 0: recomputed from x) and their sin / cos; the saved-stream
       // variant issues their loads here, under the sine reverse and the sums
-      floatx4 zp[S];
       if constexpr (SAVED && j > 1) zload(j - 1, zp);
       sine_rev<S, LAP>(hb, zc, sn, cs);  // hb = z̄_j
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = sum16(hb[0][r]);
-        if (c == 0) sacc[sb + (long)(j - 1) * W + n0 + r] += v;
+      {  // db_j: four sums at once, one owner-lane update (b128)
+        const floatx4 v = sum16x4(hb[0]);
+        if (c == 0) *reinterpret_cast<floatx4*>(sacc + sb + (long)(j - 1) * W + n0) += v;
       }
       if constexpr (j == 1) {
 #pragma unroll
@@ -595,8 +602,7 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
       const float zsc = ldexpf(1.f, e);
       const int col = c * LDB + n0;
       {
-        floatx4 snp, csp;
-        fb_sincos(zp[0], snp, csp);
+        fb_sincos(zp[0], snp, csp);  // kept: the next layer's sn / cs
 #pragma unroll
         for (int s = 0; s < S; ++s) {
         const float f2 = s == 0 ? 1.f : ((LAP && s == S - 1) ? zhl : zht);
@@ -690,9 +696,6 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
       const float zun = ldexpf(1.f, -e) / kF16WScale;
 #pragma unroll
       for (int s = 0; s < S; ++s) hb[s] = (nh[s] * zun) * (s == 0 ? 1.f : ((LAP && s == S - 1) ? bhl : bht));
-#pragma unroll
-      for (int s = 0; s < S; ++s) zc[s] = zp[s];
-      fb_sincos(zc[0], sn, cs);
       FB_STAMP(sp + 4);
     };
     if constexpr (L >= 5) bwd_layer(std::integral_constant<int, 5>{});
@@ -701,24 +704,27 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
     if constexpr (L >= 2) bwd_layer(std::integral_constant<int, 2>{});
     bwd_layer(std::integral_constant<int, 1>{});
 
-    // first layer (K = d_in: exact fp32 VALU): zc = z_0 streams, sn / cs of z_0
-    sine_rev<S, LAP>(hb, zc, sn, cs);  // hb = z̄_0
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float v = sum16(hb[0][r]);
-      if (c == 0) sacc[(long)W * din + n0 + r] += v;
+    // first layer (K = d_in: exact fp32 VALU): the z_0 streams and their sin / cos, left by layer 1
+    sine_rev<S, LAP>(hb, zq[L & 1], snq[L & 1], csq[L & 1]);  // hb = z̄_0
+    {
+      const floatx4 v = sum16x4(hb[0]);
+      if (c == 0) *reinterpret_cast<floatx4*>(sacc + (long)W * din + n0) += v;
     }
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk) {
       if (kk >= din) break;
+      floatx4 v;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float v = hb[0][r] * xk[kk];
+        v[r] = hb[0][r] * xk[kk];
 #pragma unroll
         for (int i = 0; i < NTAN; ++i)
-          if (i == kk) v += hb[1 + i][r];
-        v = sum16(v);
-        if (c == 0) sacc[(long)(n0 + r) * din + kk] += v;
+          if (i == kk) v[r] += hb[1 + i][r];
+      }
+      v = sum16x4(v);
+      if (c == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sacc[(long)(n0 + r) * din + kk] += v[r];
       }
     }
     FB_STAMP(31);

@@ -87,9 +87,14 @@ using Frag3 = FragQ<3>;
 template <int NQ>
 __device__ __forceinline__ void splitq(float a, float b, unsigned (&o)[np_of<NQ>()]) {
   if constexpr (NQ == 4) {  // fp16 hi + lo (the caller applied the power-of-two scale)
+    // the low terms a - float(hi) (exact) straight from the packed pair: one mixed-precision FMA each,
+    // fma(hi, -1, a) with the fp16 half picked by op_sel -- 4 VALU ops per pair instead of the 8 of
+    // convert / convert back / subtract per value (the compiler folds the C++ fma back into those)
     o[0] = pk_f16(a, b);
-    const f16x2v h = __builtin_bit_cast(f16x2v, o[0]);
-    o[1] = pk_f16(a - (float)h[0], b - (float)h[1]);
+    float ra, rb;
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(ra) : "v"(o[0]), "v"(a));
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rb) : "v"(o[0]), "v"(b));
+    o[1] = pk_f16(ra, rb);
     return;
   }
   o[0] = pk_bf16(a, b);

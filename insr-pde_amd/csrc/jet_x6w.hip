@@ -26,6 +26,24 @@ int wsplit_launch(const float* prm, int din, int dout, int L, int W, float* plan
   (void)dout;
   return (int)hipGetLastError();
 }
+// probe of the f16x3 operand split (insr_split_f16, tests): pair i of `in` through splitq<4> -- the
+// split of every fp16 plane, weights and streams alike -- into its packed high and low words
+static __global__ __launch_bounds__(256) void split_f16_probe_kernel(const float* __restrict__ in,
+                                                                     unsigned* __restrict__ hi,
+                                                                     unsigned* __restrict__ lo, long npairs) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= npairs) return;
+  unsigned t[2];
+  splitq<4>(in[2 * i], in[2 * i + 1], t);
+  hi[i] = t[0];
+  lo[i] = t[1];
+}
+int split_f16_probe_launch(const float* in, unsigned* hi, unsigned* lo, long npairs, hipStream_t st) {
+  if (npairs <= 0) return 0;
+  hipLaunchKernelGGL(split_f16_probe_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, in, hi, lo,
+                     npairs);
+  return (int)hipGetLastError();
+}
 void wide_launch_threads(long n, int din, int dout, int L, int W, int S, long* out) {
   wide_launch_threads_impl(n, din, dout, L, W, S, out);
 }
