@@ -359,6 +359,66 @@ __device__ __forceinline__ floatx4 load_zs(const float* base, int s, int rt, int
   return *reinterpret_cast<const floatx4*>(base + ((s * NT + rt) * 64 + lane) * 4);
 }
 
+// ---- the forward's per-tile bounds table ----
+// this lane's bounds of a sine layer's h-streams from its z-streams: tangents w |t|, Laplacian
+// w |q| + w^2 sum t^2 (the scales of the fp16 operand planes of h, forward and reverse, derive from
+// the tile's maxima of these two)
+template <int S, bool LAP>
+__device__ __forceinline__ void h_bounds(const floatx4 (&z)[S], float& mt, float& ml) {
+  constexpr int NTAN = LAP ? S - 2 : S - 1;
+  mt = 0.f;
+  ml = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float t2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NTAN; ++i) {
+      t2 = fmaf(z[1 + i][r], z[1 + i][r], t2);
+      mt = fmaxf(mt, fabsf(z[1 + i][r]));
+    }
+    if constexpr (LAP) ml = fmaxf(ml, fmaf(OMEGA, fabsf(z[S - 1][r]), OMEGA2 * t2));
+  }
+  mt *= OMEGA;
+}
+// A forward that saves the streams of a jet the saved-stream reverse sweep serves (jet_fb.hpp: W = 128,
+// the 2-d Laplacian jet S = 4 and the 2-d gradient jet S = 3) also leaves, per tile, the maxima of
+// these two bounds over the tile's 16 points x W neurons for every layer j = 0 .. L - 1 ([j][2] floats:
+// tangents, Laplacian): the sweep scales its h planes by them without waiting for the streams
+// themselves.  Home: the start of layer 0's stream-1 slot of the tile -- layer 0 saves its value stream
+// only (l0_rebuilt), so no stream is ever written or read there.
+template <int NT, int S, bool LAP>
+constexpr bool act_has_bounds() {
+  return NT == 8 && ((S == 4 && LAP) || (S == 3 && !LAP));
+}
+__device__ __forceinline__ float* act_bounds(float* act, int ntiles, int tile, int S, int NT) {
+  return act_base(act, 0, ntiles, tile, S, NT) + NT * 256;
+}
+__device__ __forceinline__ const float* act_bounds(const float* act, int ntiles, int tile, int S, int NT) {
+  return act_base(act, 0, ntiles, tile, S, NT) + NT * 256;
+}
+// lane l < 2 gets class l's wave maximum (bit pattern) of this lane's two bounds
+__device__ __forceinline__ unsigned bounds_wave_max(float mt, float ml, int lane) {
+  const unsigned u[5] = {__builtin_bit_cast(unsigned, mt), __builtin_bit_cast(unsigned, ml), 0u, 0u, 0u};
+  return wave_umax_classes<2>(u, lane);
+}
+// layer 0's pair, the same for every tile (tangents: the W_0 columns, Laplacian stream 0), by one wave
+// from W_0 itself: lane l < 2 gets class l
+template <int S, bool LAP, int W>
+__device__ __forceinline__ unsigned l0_bounds_wave(const float* w0, int din, int lane) {
+  constexpr int NTAN = LAP ? S - 2 : S - 1;
+  static_assert(W <= 256, "four rows per lane");
+  floatx4 z[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) z[s] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int r = 0; r < W / 64; ++r)
+#pragma unroll
+    for (int i = 0; i < NTAN; ++i) z[1 + i][r] = w0[(long)(lane + 64 * r) * din + i];
+  float mt, ml;
+  h_bounds<S, LAP>(z, mt, ml);
+  return bounds_wave_max(mt, ml, lane);
+}
+
 // h-stream s of a sine layer (for the weight gradient of the layer above),
 // rebuilt from saved z-streams + cached sin/cos (l0: the first layer's rebuilt streams, above).
 template <int NT, int S, bool LAP>

@@ -139,25 +139,6 @@ __device__ __forceinline__ floatx4 fb_h(int s, const floatx4 (&z)[S], const floa
   return out;
 }
 
-// this lane's bounds of a sine layer's h-streams: tangents w |t|, Laplacian w |q| + w^2 sum t^2
-template <int S, bool LAP>
-__device__ __forceinline__ void fb_h_bounds(const floatx4 (&z)[S], float& mt, float& ml) {
-  constexpr int NTAN = LAP ? S - 2 : S - 1;
-  mt = 0.f;
-  ml = 0.f;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float t2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NTAN; ++i) {
-      t2 = fmaf(z[1 + i][r], z[1 + i][r], t2);
-      mt = fmaxf(mt, fabsf(z[1 + i][r]));
-    }
-    if constexpr (LAP) ml = fmaxf(ml, fmaf(OMEGA, fabsf(z[S - 1][r]), OMEGA2 * t2));
-  }
-  mt *= OMEGA;
-}
-
 // SEED (saved streams only): the in-kernel adjoint seeds of FbJobs::seeds, a separate instantiation so the
 // pointer-seeded kernel is unchanged
 template <int S, bool LAP, int L, int ZR, bool SAVED, bool SEED = false>
@@ -369,6 +350,11 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
 #pragma unroll
       for (int s = 0; s < S; ++s) z[s] = *reinterpret_cast<const floatx4*>(base + ((s * NT + rt) * 64 + lane) * 4);
     };
+    // ... and the tile's bounds of h_0 .. h_{L-1} ([layer][tangents, Laplacian]) from the table the forward left
+    // beside them (jet_common.hpp act_bounds), issued with the x loads: lane i holds entry i, read back as
+    // scalars behind z_L's arrival below -- no layer waits for its z loads before the block-maximum barrier
+    float hbv = 0.f;
+    if constexpr (SAVED && S > 1) hbv = act_bounds(actk, ntk, lt, S, NT)[lane < 2 * L ? lane : 0];
     if constexpr (!SAVED) {
       const int i = tid, s = i / 48, o = (i / 16) % 3, pp = lt * 16 + (i & 15);
       if (s < S && o < dout && pp < N) {
@@ -408,7 +394,7 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
     auto put_h = [&](auto jc, bool stage_seeds) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-      if constexpr (S > 1) fb_h_bounds<S, LAP>(a, m[0], m[1]);
+      if constexpr (S > 1) h_bounds<S, LAP>(a, m[0], m[1]);
       if (stage_seeds && tid < S * 48) seed[tid] = sdv;
       // + every wave's reads of P (this layer's B operand) done
       exchange(m, std::integral_constant<int, (S > 1 ? (LAP ? 2 : 1) : 0)>{});
@@ -490,6 +476,13 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
       }
       fb_sincos(zc[0], snq[0], csq[0]);
     }
+    if constexpr (SAVED && S > 1) {  // h_j's powers of two, as the recompute forward leaves them
+#pragma unroll
+      for (int j = 0; j < L; ++j)
+#pragma unroll
+        for (int cl = 0; cl < (LAP ? 2 : 1); ++cl)
+          eh[j][cl] = f16_exp_for(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hbv), 2 * j + cl)));
+    }
     // output layer (exact fp32 VALU): hb = W_out^T g, dW_out / db_out into the compact row
     floatx4 hb[S];
 #pragma unroll
@@ -564,8 +557,8 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
 #pragma unroll
         for (int s = 0; s < S; ++s) zp[s] = zr[j - 1 - NZL - 1][s];
       }
-      // classes: |z̄| value, tangents, Laplacian; h_{j-1}'s bounds (tangents, Laplacian): the forward's
-      // scales eh[j - 1], or (saved streams) this exchange's classes 3, 4
+      // classes: |z̄| value, tangents, Laplacian; h_{j-1}'s scales are the forward's (eh[j - 1]: this kernel's
+      // own forward, or the bounds table of the one that saved the streams)
       float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < S; ++s)
@@ -574,19 +567,15 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
           const int cl = s == 0 ? 0 : ((LAP && s == S - 1) ? 2 : 1);
           m[cl] = fmaxf(m[cl], fabsf(hb[s][r]));
         }
-      if constexpr (SAVED && S > 1) fb_h_bounds<S, LAP>(zp, m[3], m[4]);
+      // (saved streams: stamps 1..L are free -- no forward; what precedes the exchange gets its own interval)
+      if constexpr (SAVED && L <= 4) FB_STAMP(1 + L - j);
       FB_STAMP(sp);
       // + every wave's reads of P / H (the previous layer's / the forward's) done
-      exchange(m, std::integral_constant<int, (S == 1 ? 1 : (SAVED ? 5 : (LAP ? 3 : 2)))>{});
+      exchange(m, std::integral_constant<int, (S == 1 ? 1 : (LAP ? 3 : 2))>{});
       FB_STAMP(sp + 1);
       int eht = 0, ehl = 0;
-      if constexpr (SAVED) {
-        if constexpr (S > 1) eht = f16_exp_for(m[3]);
-        if constexpr (LAP) ehl = f16_exp_for(m[4]);
-      } else {
-        if constexpr (S > 1) eht = eh[j - 1][0];
-        if constexpr (LAP) ehl = eh[j - 1][1];
-      }
+      if constexpr (S > 1) eht = eh[j - 1][0];
+      if constexpr (LAP) ehl = eh[j - 1][1];
       const float bht = ldexpf(1.f, eht), bhl = ldexpf(1.f, ehl);   // h's tangent / Laplacian scales
       const float zht = ldexpf(1.f, -eht), zhl = ldexpf(1.f, -ehl);  // ... and the matching z̄ factors
       int e = f16_exp_for(fmaxf(m[0], fmaxf(m[1] * zht, m[2] * zhl)));

@@ -36,9 +36,11 @@ struct SplitGeo {
 
 constexpr size_t kLdsMax = 163840;  // 160 KB per CU on gfx950
 
-template <int NT, int S, int T>
+template <int NT, int S, bool LAP, int T>
 constexpr size_t fwd_split_lds_bytes() {
-  return (size_t)T * S * SplitGeo<NT>::PLANE * sizeof(float);
+  // + the waves' per-tile maxima [T][2][8] of a forward that leaves the bounds table (act_has_bounds)
+  return (size_t)T * S * SplitGeo<NT>::PLANE * sizeof(float) +
+         (act_has_bounds<NT, S, LAP>() ? T * 2 * 8 * sizeof(float) : 0);
 }
 // backward: zb planes point-major with row W+8 (conflict-free ds_read_b128 rows for
 // the propagation B operand, 4 b32 column reads for the dW A operand); h planes
@@ -63,6 +65,8 @@ __global__ __launch_bounds__(SplitGeo<NT>::THREADS) void jet_fwd_split(
   const int ntiles = ((N + 63) / 64) * 4;
   const int tile0 = blockIdx.x * T;
   const int rt0 = wave * RPW;
+  constexpr bool TAB = act_has_bounds<NT, S, LAP>();
+  unsigned* bmx = reinterpret_cast<unsigned*>(lds + T * S * PLANE);  // [T][2][8] after the planes (TAB)
 
   float xv[T][3];
 #pragma unroll
@@ -143,6 +147,19 @@ __global__ __launch_bounds__(SplitGeo<NT>::THREADS) void jet_fwd_split(
           }
         }
       }
+      if constexpr (TAB) {  // this wave's bounds of h_j per tile (jet_common.hpp h_bounds), for the table below
+        if (act && j < L) {
+          int ln = lane;  // opaque: nothing derived from it is carried across the layer loop in a register
+          asm volatile("" : "+v"(ln));
+#pragma unroll
+          for (int t = 0; t < T; ++t) {
+            float mt, ml;
+            h_bounds<S, LAP>(a[t][0], mt, ml);
+            const unsigned w = bounds_wave_max(mt, ml, ln);
+            if (ln < 2) bmx[(t * 2 + ln) * 8 + wave] = w;
+          }
+        }
+      }
       __syncthreads();  // every wave has read layer j-1
     }
     if (act) {  // the first layer: its value stream only (l0_rebuilt, jet_common.hpp)
@@ -155,6 +172,28 @@ __global__ __launch_bounds__(SplitGeo<NT>::THREADS) void jet_fwd_split(
 #pragma unroll
           for (int s = 0; s < S; ++s)
             if (s < ns) *reinterpret_cast<floatx4*>(base + ((s * NT + rt0 + i) * 64 + lane) * 4) = a[t][i][s];
+      }
+      if constexpr (TAB) {  // the bounds table: h_j's pair of every tile (jet_common.hpp act_bounds)
+        if (j < L) {
+          int tq = threadIdx.x;  // (opaque, as above)
+          asm volatile("" : "+v"(tq));
+          if (j > 0) {  // the waves' slots, ordered by the barrier above (rewritten after the next one)
+            const int t = tq >> 1, cl = tq & 1;
+            if (t < T) {
+              const unsigned* q = bmx + (t * 2 + cl) * 8;
+              unsigned v = q[0];
+#pragma unroll
+              for (int w = 1; w < WV; ++w) v = max(v, q[w]);
+              act_bounds(act, ntiles, tile0 + t, S, NT)[2 * j + cl] = __builtin_bit_cast(float, v);
+            }
+          } else if (tq < 64) {  // layer 0: W_0's pair, the same for every tile, by wave 0
+            const unsigned w = l0_bounds_wave<S, LAP, W>(prm, din, tq);
+            if (tq < 2) {
+#pragma unroll
+              for (int t = 0; t < T; ++t) act_bounds(act, ntiles, tile0 + t, S, NT)[tq] = __builtin_bit_cast(float, w);
+            }
+          }
+        }
       }
     }
 #pragma unroll
@@ -562,7 +601,7 @@ __global__ __launch_bounds__(SplitGeo<NT>::THREADS) void jet_bwd_split(
 template <int NT, int S, bool LAP, int T>
 int launch_fwd_split_t(const float* x, int N, int din, int dout, int L, const float* prm, float* y, float* dy,
                        float* lap, float* act, hipStream_t st) {
-  constexpr size_t lds = fwd_split_lds_bytes<NT, S, T>();
+  constexpr size_t lds = fwd_split_lds_bytes<NT, S, LAP, T>();
   if constexpr (lds > kLdsMax) {
     return INSR_EINVAL;
   } else {

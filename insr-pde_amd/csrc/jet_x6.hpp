@@ -182,11 +182,15 @@ struct X6Geo {
   static constexpr int THREADS = 64 * WV;
 };
 
-template <int NQ, int NT, int S, int T>
+template <int NQ, int NT, int S, bool LAP, int T>
 constexpr size_t fwd_x6_lds_bytes() {
   using G = X6Geo<NT>;
-  // f16x3: + [2][T][waves] floats after the planes (the per-tile Laplacian-stream maxima, fwd_x6_block)
-  const size_t planes = (size_t)T * S * np_of<NQ>() * G::PLANE * 2 + (NQ == 4 ? (2 * T * 8 + 2 + 8) * sizeof(float) : 0);
+  // f16x3: + [2][T][waves] floats after the planes (the per-tile Laplacian-stream maxima, fwd_x6_block), the
+  // tangent flags [2] and the rare branch's wave maxima [8]; a forward that leaves the bounds table
+  // (act_has_bounds; LAP only matters at S = 3, 4): two classes of maxima, [2][T][2][waves]
+  const size_t planes = (size_t)T * S * np_of<NQ>() * G::PLANE * 2 +
+                        (act_has_bounds<NT, S, LAP>() ? (4 * T * 8 + 2 + 8) * sizeof(float)
+                                                      : (NQ == 4 ? (2 * T * 8 + 2 + 8) * sizeof(float) : 0));
   const size_t red = (size_t)G::WV * T * S * 3 * 16 * sizeof(float);  // output-layer combine
   return planes > red ? planes : red;
 }
@@ -267,9 +271,16 @@ __device__ __forceinline__ void fwd_x6_block(const float* __restrict__ x, int N,
   const int ntiles = ((N + 63) / 64) * 4;
   const int rt0 = wave * RPW;
   const u32x4* wsp = wsp_base(prm, din, dout, L, W);
-  // f16x3 Laplacian jets: the waves' per-tile maxima of the Laplacian-stream bound [2][T][8] after the
-  // planes, and the unscale of the next layer's Laplacian-stream products per tile
+  // the waves' per-tile maxima of the tangent / Laplacian bounds of h_j (jet_common.hpp h_bounds)
+  // [layer parity][T][class][8] after the planes: f16x3 Laplacian jets scale their Laplacian planes by the
+  // tile's (LSC); a forward that saves the streams of a jet the saved-stream reverse sweep serves (TAB:
+  // act_has_bounds) leaves both per tile in act for that sweep (act_bounds).  usl: the unscale of the next
+  // layer's Laplacian-stream products per tile
+  // (NC classes per tile: the Laplacian bound alone where no table is left -- those kernels are as they were)
+  constexpr bool LSC = NQ == 4 && LAP, TAB = act_has_bounds<NT, S, LAP>();
+  constexpr int NC = TAB ? 2 : 1, CL = NC - 1;  // CL: the Laplacian class
   float* zmx = lds_f + (T * S * np_of<NQ>() * PLANE) / 2;
+  unsigned* zmxu = reinterpret_cast<unsigned*>(zmx);
   float usl[T];
 #pragma unroll
   for (int t = 0; t < T; ++t) usl[t] = 1.f / kF16WScale;
@@ -281,7 +292,7 @@ __device__ __forceinline__ void fwd_x6_block(const float* __restrict__ x, int N,
   // t = the W_0 columns, bounded by every wave from W_0 itself).  ust: the next layer's tangent
   // unscale (block-uniform, scalar).
   float ust = 1.f / kF16WScale;
-  int* tflag = reinterpret_cast<int*>(zmx + 2 * T * 8);  // [2] by layer parity, then [8] wave maxima
+  int* tflag = reinterpret_cast<int*>(zmx + 2 * NC * T * 8);  // [2] by layer parity, then [8] wave maxima
   if constexpr (NQ == 4 && NTAN > 0) {
     if (threadIdx.x < 2) tflag[threadIdx.x] = 0;  // ordered before the first reader by layer 0's barrier
   }
@@ -356,9 +367,22 @@ __device__ __forceinline__ void fwd_x6_block(const float* __restrict__ x, int N,
         }
       }
     }
-    // f16x3 Laplacian jets: this wave's bound of |ddh| per tile for the planes of layer j (before the
-    // barrier the next layer's operand writes wait on anyway; j = 0 adds one)
-    if constexpr (NQ == 4 && LAP) {
+    // this wave's bounds of the h-streams of layer j per tile (before the barrier the next layer's operand
+    // writes wait on anyway; j = 0 adds one for the f16x3 Laplacian jets -- the table's layer-0 pair of
+    // the others comes from W_0, below): both classes in one packed reduction on the bit patterns
+    if constexpr (TAB) {
+      if (j < L && (LSC || (act && j > 0))) {
+        int ln = lane;  // opaque: nothing derived from it is carried across the layer loop in a register
+        asm volatile("" : "+v"(ln));
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+          float mt, ml;
+          h_bounds<S, LAP>(a[t][0], mt, ml);
+          const unsigned w = bounds_wave_max(mt, ml, ln);
+          if (ln < 2) zmxu[(((j & 1) * T + t) * 2 + ln) * 8 + wave] = w;
+        }
+      }
+    } else if constexpr (LSC) {
       if (j < L) {
 #pragma unroll
         for (int t = 0; t < T; ++t) {
@@ -436,6 +460,29 @@ __device__ __forceinline__ void fwd_x6_block(const float* __restrict__ x, int N,
           for (int s = 0; s < S; ++s)
             if (s < ns) *reinterpret_cast<floatx4*>(base + ((s * NT + rt0 + i) * 64 + lane) * 4) = a[t][i][s];
       }
+      if constexpr (TAB) {  // the bounds table: h_j's pair of every tile (jet_common.hpp act_bounds)
+        if (j < L) {
+          int tq = threadIdx.x;  // (opaque, as above)
+          asm volatile("" : "+v"(tq));
+          if (j > 0 || LSC) {  // the waves' slots, ordered by the barrier above: thread (t, class) folds them
+            const int t = tq >> 1, cl = tq & 1;
+            if (t < cnt && t < T) {
+              const unsigned* q = zmxu + (((j & 1) * T + t) * 2 + cl) * 8;
+              unsigned v = q[0];
+#pragma unroll
+              for (int w = 1; w < WV; ++w) v = max(v, q[w]);
+              act_bounds(act, ntiles, tile0 + t, S, NT)[2 * j + cl] = __builtin_bit_cast(float, v);
+            }
+          } else if (tq < 64) {  // layer 0 without that barrier: W_0's pair, the same for every tile, by wave 0
+            const unsigned w = l0_bounds_wave<S, LAP, W>(prm, din, tq);
+            if (tq < 2) {
+#pragma unroll
+              for (int t = 0; t < T; ++t)
+                if (t < cnt) act_bounds(act, ntiles, tile0 + t, S, NT)[tq] = __builtin_bit_cast(float, w);
+            }
+          }
+        }
+      }
     }
 #pragma unroll
     for (int t = 0; t < T; ++t) sine_jet<RPW, S, LAP>(a[t]);
@@ -445,9 +492,10 @@ __device__ __forceinline__ void fwd_x6_block(const float* __restrict__ x, int N,
       for (int t = 0; t < T; ++t) {
         sll[t] = 1.f;
         if constexpr (NQ == 4 && LAP) {
-          float m = zmx[((j & 1) * T + t) * 8];
+          const float* q = zmx + (((j & 1) * T + t) * NC + CL) * 8;
+          float m = q[0];
 #pragma unroll
-          for (int w = 1; w < WV; ++w) m = fmaxf(m, zmx[((j & 1) * T + t) * 8 + w]);
+          for (int w = 1; w < WV; ++w) m = fmaxf(m, q[w]);
           const int e = f16_exp_for(m);
           sll[t] = ldexpf(1.f, e);
           usl[t] = ldexpf(1.f, -e) / kF16WScale;
@@ -616,9 +664,9 @@ constexpr int kMixAdvT = INSR_MIX_ADV_T;
 
 template <int NQ, int NT, int DIN, int BODIES>
 constexpr size_t fwd_mix_lds_bytes() {
-  constexpr size_t a = (BODIES & (kMixV | kMixA)) ? fwd_x6_lds_bytes<NQ, NT, 1, 2>() : 0;
-  constexpr size_t b = (BODIES & kMixG) ? fwd_x6_lds_bytes<NQ, NT, 1 + DIN, 1>() : 0;
-  constexpr size_t c = (DIN <= 2 && (BODIES & kMixL)) ? fwd_x6_lds_bytes<NQ, NT, 2 + DIN, 1>() : 0;
+  constexpr size_t a = (BODIES & (kMixV | kMixA)) ? fwd_x6_lds_bytes<NQ, NT, 1, false, 2>() : 0;
+  constexpr size_t b = (BODIES & kMixG) ? fwd_x6_lds_bytes<NQ, NT, 1 + DIN, false, 1>() : 0;
+  constexpr size_t c = (DIN <= 2 && (BODIES & kMixL)) ? fwd_x6_lds_bytes<NQ, NT, 2 + DIN, true, 1>() : 0;
   return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
@@ -723,7 +771,7 @@ int launch_fwd_x6_multi_t(const InsrJetJob* jobs, const int* small, const int* n
   // 1-tile blocks for small jobs only beside T >= 4 blocks: with T <= 2 the second body would
   // raise the kernel's registers (T = 2 value: 84 vs 62 VGPRs, two blocks per CU fewer)
   constexpr int TB = T <= 2 ? T : 1;
-  constexpr size_t lds = fwd_x6_lds_bytes<NQ, NT, S, T>();
+  constexpr size_t lds = fwd_x6_lds_bytes<NQ, NT, S, LAP, T>();
   if constexpr (lds > kLdsMax) {
     return INSR_EINVAL;
   } else {
@@ -757,7 +805,7 @@ int launch_fwd_x6_multi_t(const InsrJetJob* jobs, const int* small, const int* n
 template <int NQ, int NT, int S, bool LAP, int T>
 int launch_fwd_x6_t(const float* x, int N, int din, int dout, int L, const float* prm, float* y, float* dy,
                     float* lap, float* act, int nbal, hipStream_t st) {
-  constexpr size_t lds = fwd_x6_lds_bytes<NQ, NT, S, T>();
+  constexpr size_t lds = fwd_x6_lds_bytes<NQ, NT, S, LAP, T>();
   if constexpr (lds > kLdsMax) {
     return INSR_EINVAL;
   } else {

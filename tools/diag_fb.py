@@ -5,7 +5,9 @@
 Stamps per tile (block 0, every wave, first 8 tiles): the forward's layer 0 + its planes, per hidden
 layer the MFMAs and the planes of the next, the output-layer reverse, per reverse layer the sine
 reverse, the block-maximum exchange (barrier), the P / H writes (+ barrier), the dW MFMAs, the
-propagation; cycles (s_memtime ticks), median over the waves and tiles.
+propagation; cycles (s_memtime ticks), median over the waves and tiles.  The saved-stream variant
+(--policy 5, 4 layers) has one more stamp per reverse layer, between the sine reverse / db sums and the
+exchange: what precedes the barrier gets its own interval.
 """
 import argparse
 import ctypes
@@ -25,7 +27,9 @@ def phases(L, saved=False):
         prev = 10
         for j in range(L, 0, -1):
             sp = 11 + 5 * (L - j)
-            names += [(prev, sp, f"rev L{j} sine_rev+z"), (sp, sp + 1, f"rev L{j} exchange"),
+            mid = 1 + L - j  # the stamp between the sine reverse / db sums and what precedes the exchange
+            names += [(prev, mid, f"rev L{j} sine_rev+sums"), (mid, sp, f"rev L{j} pre-exchange"),
+                      (sp, sp + 1, f"rev L{j} exchange"),
                       (sp + 1, sp + 2, f"rev L{j} P/H writes"), (sp + 2, sp + 3, f"rev L{j} dW"),
                       (sp + 3, sp + 4, f"rev L{j} prop")]
             prev = sp + 4
