@@ -907,7 +907,8 @@ __device__ __forceinline__ void put_neuron_major(unsigned short* P, const floatx
 
 // LDS images of one stream group: Z point-major [q][16 p][W + 8] (the propagation B operand,
 // and the dW A operand through u16 column reads), H neuron-major [q][m][16 p] (the dW B
-// operand, one b128 per plane; written through a quad transpose: one b64 store per plane).
+// operand, one b128 per plane; written through a quad transpose: one b64 store per plane;
+// x6_bwd_pm shapes: H as Z, ZSET elements per set).
 template <int NQ, int NT>
 struct X6BwdGeo {
   using G = X6Geo<NT>;
@@ -921,10 +922,23 @@ struct X6BwdGeo {
   static constexpr size_t SET_BYTES = (size_t)(ZSET + HSET) * 2;
 };
 
+// The f16x3 value backward at W = 128 (one row tile per wave, one stream group) keeps H point-major
+// like Z -- [q][16 p][W + 8], one lds_put4 per granule, no quad transpose -- and reads both dW
+// operands with the transpose read; its waves tile dW 2 row tiles x 4 column tiles (jet_bwd_x6)
+template <int NQ, int NT, int S>
+constexpr bool x6_bwd_pm() {
+  return NQ == 4 && NT == 8 && S == 1;
+}
+template <int NQ, int NT, int S>
+constexpr size_t x6_bwd_set_bytes() {
+  using BG = X6BwdGeo<NQ, NT>;
+  return x6_bwd_pm<NQ, NT, S>() ? (size_t)2 * BG::ZSET * 2 : BG::SET_BYTES;
+}
+
 // streams per LDS group: all S if T tiles of them fit, else S/2, else 1
 template <int NQ, int NT, int S, int T>
 constexpr int x6_bwd_sg() {
-  constexpr size_t set = X6BwdGeo<NQ, NT>::SET_BYTES;
+  constexpr size_t set = x6_bwd_set_bytes<NQ, NT, S>();
   if ((size_t)T * S * set <= kLdsMax) return S;
   if (S % 2 == 0 && (size_t)T * (S / 2) * set <= kLdsMax) return S / 2;
   return 1;
@@ -938,7 +952,7 @@ constexpr size_t bwd_x6_seed_floats() {
 }
 template <int NQ, int NT, int S, int T>
 constexpr size_t bwd_x6_lds_bytes() {  // + 2 x 5 x 8 floats: the waves' per-layer maxima (NQ = 4)
-  return (size_t)T * x6_bwd_sg<NQ, NT, S, T>() * X6BwdGeo<NQ, NT>::SET_BYTES + 2 * 5 * 8 * sizeof(float) +
+  return (size_t)T * x6_bwd_sg<NQ, NT, S, T>() * x6_bwd_set_bytes<NQ, NT, S>() + 2 * 5 * 8 * sizeof(float) +
          bwd_x6_seed_floats<S, T>() * sizeof(float);
 }
 
@@ -949,7 +963,9 @@ __global__ __launch_bounds__(X6Geo<NT>::THREADS) void jet_bwd_x6(const BwdJobsX6
   using G = X6Geo<NT>;
   using BG = X6BwdGeo<NQ, NT>;
   constexpr int W = G::W, RPW = G::RPW, KC = G::KC;
-  constexpr int LDB = BG::ZROW, ZPLANE = BG::ZPLANE, ZSET = BG::ZSET, HPLANE = BG::HPLANE, HSET = BG::HSET;
+  constexpr bool PM = x6_bwd_pm<NQ, NT, S>();  // point-major H, tiled dW, streamed W^T
+  constexpr int LDB = BG::ZROW, ZPLANE = BG::ZPLANE, ZSET = BG::ZSET, HPLANE = BG::HPLANE;
+  constexpr int HSET = PM ? BG::ZSET : BG::HSET;
   constexpr int NTAN = LAP ? S - 2 : S - 1;
   constexpr int SG = x6_bwd_sg<NQ, NT, S, T>();
   constexpr int NG = S / SG;            // stream groups per layer
@@ -1249,7 +1265,7 @@ __global__ __launch_bounds__(X6Geo<NT>::THREADS) void jet_bwd_x6(const BwdJobsX6
     // pre-split planes (issued here, in flight during the dW phase).  Several stream groups:
     // re-read per group (L2 hits) instead of holding the fragments across groups
     FragQ<NQ> wt[RPW][KC];
-    if constexpr (NG == 1) {
+    if constexpr (NG == 1 && !PM) {  // (PM streams them one K chunk ahead of the propagation)
 #pragma unroll
       for (int i = 0; i < RPW; ++i)
 #pragma unroll
@@ -1359,12 +1375,98 @@ __global__ __launch_bounds__(X6Geo<NT>::THREADS) void jet_bwd_x6(const BwdJobsX6
             }
             if (lq) hs *= hll;
             if (tq) hs *= htl;
-            put_neuron_major<NQ, HPLANE>(H + u * HSET, hs, col, c);
+            if constexpr (PM)
+              lds_put4<NQ, ZPLANE>(H + u * HSET + c * LDB + col, hs[0], hs[1], hs[2], hs[3]);
+            else
+              put_neuron_major<NQ, HPLANE>(H + u * HSET, hs, col, c);
           }
       }
       INSR_STAMP(L - j, 4);
       __syncthreads();
       INSR_STAMP(L - j, 5);
+      if constexpr (PM) {
+        // the propagation's first W^T fragment: its L2 latency runs under the dW MFMAs
+        FragQ<NQ> wn = wsp_frag<NQ, NT>(wsp, L, 1, j, rt0, 0, lane);
+        // dW_j: wave (ra, cb) = (wave >> 1, wave & 1) owns row tiles 2 ra, 2 ra + 1 (A: column reads of
+        // the Z sets) x column tiles 4 cb .. 4 cb + 3 (B: the same transpose reads of the H sets; lane c
+        // receives neuron c at the chunk's 8 points, the K placement of A) -- 6 fragment reads per 8
+        // MFMA triples (a wave owning one row tile x all 8 column tiles: 9)
+        const int ra = wave >> 1, cb = wave & 1;
+        floatx4 dq[NT];
+#pragma unroll
+        for (int q = 0; q < NT; ++q) dq[q] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+          if (2 * ch >= cnt) break;  // unused tile slots of a balanced block
+          const int u = 2 * ch + (g >> 1);
+          const bool live = u < cnt;
+          const int p0 = 8 * (g & 1);
+          const int lo_ = (p0 + (c >> 2)) * LDB + 4 * (c & 3);
+          FragQ<NQ> af[2];
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const unsigned short* pa = Z + (live ? u : 0) * ZSET + lo_ + 16 * (2 * ra + i);
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+              const v4s lo = ds_read_tr16(pa + q * ZPLANE);
+              const v4s hi = ds_read_tr16(pa + q * ZPLANE + 4 * LDB);
+              const u32x2 wl = __builtin_bit_cast(u32x2, lo), wh = __builtin_bit_cast(u32x2, hi);
+              af[i].q[q] = live ? u32x4{wl[0], wl[1], wh[0], wh[1]} : u32x4{0u, 0u, 0u, 0u};
+            }
+          }
+          // the next column tile's B fragment is issued before this one's MFMAs
+          auto bfrag = [&](int q4) __attribute__((always_inline)) {
+            FragQ<NQ> bf;
+            const unsigned short* pb = H + (live ? u : 0) * HSET + lo_ + 16 * (4 * cb + q4);
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+              const v4s lo = ds_read_tr16(pb + q * ZPLANE);
+              const v4s hi = ds_read_tr16(pb + q * ZPLANE + 4 * LDB);
+              const u32x2 wl = __builtin_bit_cast(u32x2, lo), wh = __builtin_bit_cast(u32x2, hi);
+              bf.q[q] = u32x4{wl[0], wl[1], wh[0], wh[1]};
+            }
+            return bf;
+          };
+          FragQ<NQ> bf = bfrag(0);
+#pragma unroll
+          for (int q4 = 0; q4 < 4; ++q4) {
+            FragQ<NQ> bn;
+            if (q4 < 3) bn = bfrag(q4 + 1);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) dq[4 * i + q4] = mfma_q<NQ>(af[i], bf, dq[4 * i + q4]);
+            X6_SCHED_FENCE();
+            if (q4 < 3) bf = bn;
+          }
+        }
+        {  // this wave's 2 x 4 tiles of dW_j: store now (frees the accumulators)
+          float* dW = mypart + hidden_off(din, W, j);
+#pragma unroll
+          for (int q = 0; q < NT; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              dW[(16 * (2 * ra + q / 4) + 4 * g + r) * W + 16 * (4 * cb + q % 4) + c] = dq[q][r] * zun;
+        }
+        INSR_STAMP(L - j, 6);
+        // propagation (an unused slot of a balanced block holds zero adjoints in Z: its products are
+        // zeros).  W^T one K chunk ahead; the next (K chunk, tile) B fragment before this one's MFMAs
+#pragma unroll
+        for (int t = 0; t < T; ++t) nh[t][0][0] = floatx4{0.f, 0.f, 0.f, 0.f};
+        FragQ<NQ> pb = lds_frag<NQ, ZPLANE>(Z + c * LDB + 8 * g);
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc) {
+          const FragQ<NQ> wc = wn;
+          if (kc + 1 < KC) wn = wsp_frag<NQ, NT>(wsp, L, 1, j, rt0, kc + 1, lane);
+#pragma unroll
+          for (int t = 0; t < T; ++t) {
+            const int nk = t + 1 < T ? kc : kc + 1, nt = t + 1 < T ? t + 1 : 0;
+            FragQ<NQ> pn;
+            if (nk < KC) pn = lds_frag<NQ, ZPLANE>(Z + nt * ZSET + c * LDB + 32 * nk + 8 * g);
+            nh[t][0][0] = mfma_q<NQ>(wc, pb, nh[t][0][0]);
+            X6_SCHED_FENCE();
+            if (nk < KC) pb = pn;
+          }
+        }
+      } else {
       // dW_j rows n = 16 rt + c (A), columns m (B); K = sets x 16 points
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch) {
@@ -1433,6 +1535,7 @@ __global__ __launch_bounds__(X6Geo<NT>::THREADS) void jet_bwd_x6(const BwdJobsX6
             X6_SCHED_FENCE();
           }
         }
+      }  // !PM
     }
     INSR_STAMP(L - j, 7);
     if constexpr (NG > 1) {  // dW_j rows of this wave

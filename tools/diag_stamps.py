@@ -5,7 +5,8 @@
 Phases per layer j (L..1): 0->1 sine reverse + bias partials, 1->2 sin/cos of z_{j-1}
 (global loads), 2->3 barrier 1, 3->4 LDS writes (zb, h_{j-1}), 4->5 barrier 2,
 5->6 dW MFMAs + stores, 6->7 propagation (W^T loads + MFMAs).  Cycles, median over
-the waves of block 0 and of the middle block.
+the waves of block 0 and of the middle block.  "pm" in the x6 labels: the f16x3 value backward at
+W = 128 (jet_x6.hpp x6_bwd_pm), whose W^T fragments stream through the propagation.
 """
 import argparse
 import ctypes
@@ -18,8 +19,11 @@ import torch  # noqa: E402
 
 NETS = {"fluid_pres": (2, 1, 4, 128), "fluid_vel": (2, 2, 4, 128), "el3d": (3, 3, 5, 256)}
 PH = ["sine_rev+bias", "sincos(z_j-1)", "barrier1", "lds_write", "barrier2", "dW", "propagate"]
-# x6 backward (jet_x6.hpp): stamps of the LAST stream group of a layer
-PH_X6 = ["sine_rev+bias", "W^T frags+sincos(+prev groups)", "barrier1", "lds_write", "barrier2", "dW", "propagate"]
+# x6 backward (jet_x6.hpp): stamps of the LAST stream group of a layer.  The f16x3 value backward at
+# W = 128 (x6_bwd_pm) issues no W^T fragment in 1->2: its first one goes out at the start of dW and the
+# rest stream through the propagation, one K chunk ahead
+PH_X6 = ["sine_rev+bias", "sincos(+W^T frags unless pm)(+prev groups)", "barrier1", "lds_write", "barrier2",
+         "dW(+1st W^T frag if pm)", "propagate(+W^T stream if pm)"]
 
 
 def main():
