@@ -46,7 +46,3 @@ extern "C" int insr_diag_fb_stamps(unsigned long long* out, int n) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(insr::g_fb_stamps), (size_t)m * sizeof(unsigned long long));
 }
 #endif
-
-namespace insr {
-
-}  // namespace insr

@@ -118,7 +118,8 @@ __device__ __forceinline__ void fb_sincos(const floatx4& z, floatx4& s, floatx4&
   }
 }
 
-// h-stream s of a sine layer from its z-streams (z[1..S-1]) and sin / cos
+// h-stream s of a sine layer from its z-streams (z[1..S-1]) and sin / cos: the formulas of h_from_regs
+// (jet_x6.hpp), kept apart -- routed through it, the saved-stream Laplacian sweep compiles to other code
 template <int S, bool LAP>
 __device__ __forceinline__ floatx4 fb_h(int s, const floatx4 (&z)[S], const floatx4& sn, const floatx4& cs) {
   constexpr int NTAN = LAP ? S - 2 : S - 1;
@@ -540,9 +541,9 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
         for (int r = 0; r < 4; ++r) {
           const int n = n0 + r;
           float z = b0s[n];
-    #pragma unroll
-      for (int kk = 0; kk < 3; ++kk)
-        if (kk < din) z = fmaf(W0s[3 * n + kk], xk[kk], z);
+#pragma unroll
+          for (int kk = 0; kk < 3; ++kk)
+            if (kk < din) z = fmaf(W0s[3 * n + kk], xk[kk], z);
           zp[0][r] = z;
 #pragma unroll
           for (int i = 0; i < NTAN; ++i) zp[1 + i][r] = W0s[3 * n + i];
@@ -608,7 +609,9 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
       FragQ<4> wn = wsp_frag<4, NT>(wsl, L, 1, j, rt, 0, lane);
       // dW_j: wave (ra, cb) = (wave >> 1, wave & 1) owns row tiles 2 ra, 2 ra + 1 (A: z̄ column reads
       // of the point-major P sets) x column tiles 4 cb .. 4 cb + 3 (B: transpose reads of H) -- 6
-      // fragment reads per 8 MFMA triples (a wave owning one row tile x all 8 column tiles: 9)
+      // fragment reads per 8 MFMA triples (a wave owning one row tile x all 8 column tiles: 9).  This loop
+      // and the propagation below are also the point-major body of jet_bwd_x6 (jet_x6.hpp), with streams for
+      // tiles: a change to one belongs in the other (DESIGN.md section 14 on why they are two copies)
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch) {
         const int u = 2 * ch + (g >> 1);
@@ -617,18 +620,15 @@ __global__ __launch_bounds__(512, 1) void jet_fb_x6(const FbJobs J, int din, int
         FragQ<4> af[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-          const unsigned short* pa =
-              P + (live ? u : 0) * ZSET + (p0 + (c >> 2)) * LDB + 16 * (2 * ra + i) + 4 * (c & 3);
+          const FragQ<4> a = lds_frag_tr<4, ZPLANE, LDB>(
+              P + (live ? u : 0) * ZSET + (p0 + (c >> 2)) * LDB + 16 * (2 * ra + i) + 4 * (c & 3), live);
 #pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const v4s lo = ds_read_tr16(pa + q * ZPLANE);
-            const v4s hi = ds_read_tr16(pa + q * ZPLANE + 4 * LDB);
-            const u32x2 wl = __builtin_bit_cast(u32x2, lo), wh = __builtin_bit_cast(u32x2, hi);
-            af[i].q[q] = live ? u32x4{wl[0], wl[1], wh[0], wh[1]} : u32x4{0u, 0u, 0u, 0u};
-          }
+          for (int q = 0; q < 2; ++q) af[i].q[q] = a.q[q];  // plane by plane (lds_frag_tr)
         }
         // B: h_{j-1} rows 16 ct + c at the chunk's 8 points -- transpose reads as A; the next column
-        // tile's fragment is issued before this one's MFMAs (its LDS latency runs under them)
+        // tile's fragment is issued before this one's MFMAs (its LDS latency runs under them).  Written
+        // out, not lds_frag_tr: with the address formed once outside the plane loop the compiler swaps
+        // the two reads of a plane in every instantiation of this kernel
         auto bfrag = [&](int q4) __attribute__((always_inline)) {
           FragQ<4> bf;
 #pragma unroll

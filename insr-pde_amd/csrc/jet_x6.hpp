@@ -846,10 +846,9 @@ namespace insr {
 // reads of Z.  (Measured alternative, fp32 planes split by every reader: 1.4-2x slower --
 // the reader-side split is 8x redundant VALU work across the block's waves.)
 // h-stream s of a sine layer from the derivative z-streams held in registers
-// (zd[s - 1] = stream s >= 1) + sin/cos
+// (zd[s - 1] = stream s >= 1; never read at S = 1) + sin/cos
 template <int S, bool LAP>
-__device__ __forceinline__ floatx4 h_from_regs(int s, const floatx4 (&zd)[S - 1], const floatx4& sn,
-                                               const floatx4& cs) {
+__device__ __forceinline__ floatx4 h_from_regs(int s, const floatx4* zd, const floatx4& sn, const floatx4& cs) {
   constexpr int NTAN = LAP ? S - 2 : S - 1;
   if (s == 0) return sn;
   floatx4 out;
@@ -894,6 +893,26 @@ __device__ __forceinline__ floatx4 quad_transpose(const floatx4& v, int c) {
 typedef short v4s __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v4s ds_read_tr16(const unsigned short* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(p));
+}
+
+// one fragment by column reads of a point-major image (NQ planes PLANE elements apart, point rows
+// ROW elements apart) with the transpose read: per 16-lane group, lane 4 r + p4 addresses point row
+// r (+ 4), columns 4 p4 .. 4 p4 + 3 of 16 neurons -- p is that address in plane 0 -- and lane c
+// receives neuron c at the 8 points (2 reads per plane instead of 8 u16 reads; every lane takes
+// part: EXEC full).  Zeros when !live.  The statement order is load-bearing:
+// the select stays inside, on the assembled vector, and a caller that keeps the fragment copies it plane
+// by plane (a whole-struct copy or initialisation reorders the reads in some instantiations)
+template <int NQ, int PLANE, int ROW>
+__device__ __forceinline__ FragQ<NQ> lds_frag_tr(const unsigned short* p, bool live = true) {
+  FragQ<NQ> f;
+#pragma unroll
+  for (int q = 0; q < np_of<NQ>(); ++q) {
+    const v4s lo = ds_read_tr16(p + q * PLANE);
+    const v4s hi = ds_read_tr16(p + q * PLANE + 4 * ROW);
+    const u32x2 wl = __builtin_bit_cast(u32x2, lo), wh = __builtin_bit_cast(u32x2, hi);
+    f.q[q] = live ? u32x4{wl[0], wl[1], wh[0], wh[1]} : u32x4{0u, 0u, 0u, 0u};
+  }
+  return f;
 }
 
 // one value granule (4 neurons x 1 point per lane, C layout) -> neuron-major bf16 planes
@@ -1390,7 +1409,9 @@ __global__ __launch_bounds__(X6Geo<NT>::THREADS) void jet_bwd_x6(const BwdJobsX6
         // dW_j: wave (ra, cb) = (wave >> 1, wave & 1) owns row tiles 2 ra, 2 ra + 1 (A: column reads of
         // the Z sets) x column tiles 4 cb .. 4 cb + 3 (B: the same transpose reads of the H sets; lane c
         // receives neuron c at the chunk's 8 points, the K placement of A) -- 6 fragment reads per 8
-        // MFMA triples (a wave owning one row tile x all 8 column tiles: 9)
+        // MFMA triples (a wave owning one row tile x all 8 column tiles: 9).  This loop and the propagation
+        // below are jet_fb.hpp bwd_layer's with tiles for streams: a change to one belongs in the other
+        // (why they are two copies and not one function: DESIGN.md section 14)
         const int ra = wave >> 1, cb = wave & 1;
         floatx4 dq[NT];
 #pragma unroll
@@ -1405,27 +1426,13 @@ __global__ __launch_bounds__(X6Geo<NT>::THREADS) void jet_bwd_x6(const BwdJobsX6
           FragQ<NQ> af[2];
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            const unsigned short* pa = Z + (live ? u : 0) * ZSET + lo_ + 16 * (2 * ra + i);
+            const FragQ<NQ> a = lds_frag_tr<NQ, ZPLANE, LDB>(Z + (live ? u : 0) * ZSET + lo_ + 16 * (2 * ra + i), live);
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-              const v4s lo = ds_read_tr16(pa + q * ZPLANE);
-              const v4s hi = ds_read_tr16(pa + q * ZPLANE + 4 * LDB);
-              const u32x2 wl = __builtin_bit_cast(u32x2, lo), wh = __builtin_bit_cast(u32x2, hi);
-              af[i].q[q] = live ? u32x4{wl[0], wl[1], wh[0], wh[1]} : u32x4{0u, 0u, 0u, 0u};
-            }
+            for (int q = 0; q < 2; ++q) af[i].q[q] = a.q[q];  // plane by plane (lds_frag_tr)
           }
           // the next column tile's B fragment is issued before this one's MFMAs
           auto bfrag = [&](int q4) __attribute__((always_inline)) {
-            FragQ<NQ> bf;
-            const unsigned short* pb = H + (live ? u : 0) * HSET + lo_ + 16 * (4 * cb + q4);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-              const v4s lo = ds_read_tr16(pb + q * ZPLANE);
-              const v4s hi = ds_read_tr16(pb + q * ZPLANE + 4 * LDB);
-              const u32x2 wl = __builtin_bit_cast(u32x2, lo), wh = __builtin_bit_cast(u32x2, hi);
-              bf.q[q] = u32x4{wl[0], wl[1], wh[0], wh[1]};
-            }
-            return bf;
+            return lds_frag_tr<NQ, ZPLANE, LDB>(H + (live ? u : 0) * HSET + lo_ + 16 * (4 * cb + q4));
           };
           FragQ<NQ> bf = bfrag(0);
 #pragma unroll
@@ -1476,22 +1483,12 @@ __global__ __launch_bounds__(X6Geo<NT>::THREADS) void jet_bwd_x6(const BwdJobsX6
         const int p0 = 8 * (g & 1);
 #pragma unroll
         for (int i = 0; i < RPW; ++i) {
+          // column reads of the point-major Z image: this wave's 16 neurons at the chunk's 8 points
+          const FragQ<NQ> a = lds_frag_tr<NQ, ZPLANE, LDB>(
+              Z + (live ? u : 0) * ZSET + (p0 + (c >> 2)) * LDB + 16 * (rt0 + i) + 4 * (c & 3), live);
           FragQ<NQ> af;
-          {
-            // column reads of the point-major Z image with the gfx950 transpose read: per
-            // 16-lane group, lane 4 r + p4 addresses row p0 + r (+ 4), columns 4 p4 .. 4 p4 + 3
-            // of this wave's 16 neurons; lane c receives neuron c at 4 consecutive points
-            // (2 reads per plane instead of 8 u16 reads; every lane takes part: EXEC full)
-            const unsigned short* pa =
-                Z + (live ? u : 0) * ZSET + (p0 + (c >> 2)) * LDB + 16 * (rt0 + i) + 4 * (c & 3);
 #pragma unroll
-            for (int q = 0; q < np_of<NQ>(); ++q) {
-              const v4s lo = ds_read_tr16(pa + q * ZPLANE);
-              const v4s hi = ds_read_tr16(pa + q * ZPLANE + 4 * LDB);
-              const u32x2 wl = __builtin_bit_cast(u32x2, lo), wh = __builtin_bit_cast(u32x2, hi);
-              af.q[q] = live ? u32x4{wl[0], wl[1], wh[0], wh[1]} : u32x4{0u, 0u, 0u, 0u};
-            }
-          }
+          for (int q = 0; q < np_of<NQ>(); ++q) af.q[q] = a.q[q];  // plane by plane (lds_frag_tr)
 #pragma unroll
           for (int ct = 0; ct < NT; ++ct) {
             const FragQ<NQ> bf = lds_frag<NQ, HPLANE>(H + (live ? u : 0) * HSET + (16 * ct + c) * 16 + p0);

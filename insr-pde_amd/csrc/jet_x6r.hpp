@@ -44,17 +44,6 @@ constexpr size_t x6r_lds_bytes() {
   return (size_t)x6r_ts<S>() * S * (BG::ZSET + BG::HSET) * 2 + (size_t)kX6rSmallMax * sizeof(float);
 }
 
-// h-stream s of a sine layer from sin / cos and the derivative z-streams held in registers
-template <int S, bool LAP>
-__device__ __forceinline__ floatx4 x6r_h(int s, const floatx4 (&zk)[S > 1 ? S - 1 : 1], const floatx4& sn,
-                                         const floatx4& cs) {
-  if constexpr (S == 1) {
-    return sn;
-  } else {
-    return h_from_regs<S, LAP>(s, zk, sn, cs);
-  }
-}
-
 template <int NQ, int S, bool LAP, int L, int RPW>
 __global__ __launch_bounds__(512 / RPW, 1) void jet_bwd_x6r(const float* __restrict__ x, int N, int din, int dout,
                                                       const float* __restrict__ prm, const float* __restrict__ act,
@@ -174,7 +163,7 @@ __global__ __launch_bounds__(512 / RPW, 1) void jet_bwd_x6r(const float* __restr
         for (int t = 0; t < TS; ++t)
 #pragma unroll
           for (int s = 0; s < S; ++s) {
-            const floatx4 hs = x6r_h<S, LAP>(s, zk[t][i], sn[t][i], cs[t][i]);
+            const floatx4 hs = h_from_regs<S, LAP>(s, zk[t][i], sn[t][i], cs[t][i]);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               acc4[r] = fmaf(ga[t][s], hs[r], acc4[r]);
@@ -239,7 +228,7 @@ __global__ __launch_bounds__(512 / RPW, 1) void jet_bwd_x6r(const float* __restr
             const int u = t * S + s;
             lds_put4<NQ, ZPLANE>(Z + u * ZSET + c * LDB + 16 * (rt0 + i) + 4 * g, hb[t][i][s][0], hb[t][i][s][1],
                                  hb[t][i][s][2], hb[t][i][s][3]);
-            put_neuron_major<NQ, HPLANE>(H + u * HSET, x6r_h<S, LAP>(s, zkp[t][i], snp[t][i], csp[t][i]),
+            put_neuron_major<NQ, HPLANE>(H + u * HSET, h_from_regs<S, LAP>(s, zkp[t][i], snp[t][i], csp[t][i]),
                                          16 * (rt0 + i) + 4 * g, c);
           }
       __syncthreads();
@@ -254,14 +243,10 @@ __global__ __launch_bounds__(512 / RPW, 1) void jet_bwd_x6r(const float* __restr
         FragQ<NQ> af[RPW];
 #pragma unroll
         for (int i = 0; i < RPW; ++i) {
-          const unsigned short* pa = Z + (live ? u : 0) * ZSET + (p0 + (c >> 2)) * LDB + 16 * (rt0 + i) + 4 * (c & 3);
+          const FragQ<NQ> a = lds_frag_tr<NQ, ZPLANE, LDB>(
+              Z + (live ? u : 0) * ZSET + (p0 + (c >> 2)) * LDB + 16 * (rt0 + i) + 4 * (c & 3), live);
 #pragma unroll
-          for (int q = 0; q < NQ; ++q) {
-            const v4s lo = ds_read_tr16(pa + q * ZPLANE);
-            const v4s hi = ds_read_tr16(pa + q * ZPLANE + 4 * LDB);
-            const u32x2 wl = __builtin_bit_cast(u32x2, lo), wh = __builtin_bit_cast(u32x2, hi);
-            af[i].q[q] = live ? u32x4{wl[0], wl[1], wh[0], wh[1]} : u32x4{0u, 0u, 0u, 0u};
-          }
+          for (int q = 0; q < NQ; ++q) af[i].q[q] = a.q[q];  // plane by plane: a struct copy reorders the reads
         }
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
