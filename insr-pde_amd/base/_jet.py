@@ -379,6 +379,23 @@ def _seeded_launch(job, plan, work, st):
 SEED_STATS = {"seeded": 0}  # reverse jets that evaluated a lazy loss group's terms, in all and per jet mode
 
 
+def _splits_phases(lib, path, n, din, dout, L, W, cmode):
+    """Does this backward run as a sweep + separate sums (insr_siren_jet_bwd_grad_adam phases 1 / 2): a
+    jet_fb.hpp kernel, or the two-kernel path of a net with hidden layers (capi.hip splits_phases)."""
+    return lib.insr_jet_bwd_kernel(n, din, dout, L, W, cmode) == 1 or (path == 1 and L > 0)
+
+
+def _hand_over(mlp, pr, cur, defer, launch=True):
+    """A reverse jet's held-back sums: to the Adam launch (defer: inside defer_reductions), else launched
+    now (launch); the write of .grad ends here either way."""
+    if defer:
+        mlp.set_pending_reduce(pr)
+        _Defer.nets.append(mlp)
+    elif launch:
+        pr.launch()
+    mlp.grad_write_end(cur)
+
+
 def _launch_bwd(job):
     """One reverse jet into its network's flat .grad (first write of an iteration overwrites)."""
     mlp, mode, x2, act, gy, gdy, glap = job.mlp, job.mode, job.x2, job.act, job.gy, job.gdy, job.glap
@@ -392,6 +409,7 @@ def _launch_bwd(job):
     cur = job.cur
     st = ctypes.c_void_p(cur.cuda_stream)
     mlp.grad_write_begin(cur)  # order after a write of .grad made on another stream
+    defer = getattr(_Defer, "depth", 0) > 0  # inside defer_reductions: the sums go into the Adam launch
     path = lib.insr_jet_bwd_path(n, din, dout, L, W, cmode)
     if path > 0:
         # two-kernel path (propagation + split-K dW GEMM), the resident-dW or the recompute persistent
@@ -400,8 +418,8 @@ def _launch_bwd(job):
         with torch.cuda.stream(cur):
             work = torch.empty(max(lib.insr_jet_bwd_work_bytes(n, din, dout, L, W, cmode) // 4, 1),
                                device=x2.device, dtype=torch.float32)
-        fb_split = lib.insr_jet_bwd_kernel(n, din, dout, L, W, cmode) == 1 or (path == 1 and L > 0)
-        if plan is not None or (getattr(_Defer, "depth", 0) > 0 and fb_split):
+        splits = _splits_phases(lib, path, n, din, dout, L, W, cmode)
+        if plan is not None or (defer and splits):
             # the jet_fb.hpp or the two-kernel backward: its sweep now, its sums with the Adam launch
             # (defer_reductions) -- or, seeded outside that scope, right after it
             if plan is not None:
@@ -416,12 +434,7 @@ def _launch_bwd(job):
                 nat.check(rc, "insr_siren_jet_bwd_grad_adam")
             pr = PendingSums("split", work, 0, 0, (mlp, x2, n, cmode), gflat, accumulate, cur,
                              (mode, n, W, (din, dout, L)), fin)
-            if getattr(_Defer, "depth", 0) > 0:
-                mlp.set_pending_reduce(pr)
-                _Defer.nets.append(mlp)
-            else:
-                pr.launch()
-            mlp.grad_write_end(cur)
+            _hand_over(mlp, pr, cur, defer)
             return
         with _timed("bwd", mode, n, W, (din, dout, L)):
             rc = lib.insr_siren_jet_bwd_grad(nat.ptr(x2), n, din, dout, L, W, cmode, nat.ptr(mlp.flat_params()),
@@ -443,13 +456,7 @@ def _launch_bwd(job):
         nat.check(rc, "insr_siren_jet_bwd")
     nb, stride = lib.insr_jet_partial_blocks(n, din, W, cmode), lib.insr_jet_partial_stride(din, dout, L, W)
     pr = PendingSums("rows", part, nb, stride, mlp, gflat, accumulate, cur, (mode, n, W, (din, dout, L)), fin)
-    if getattr(_Defer, "depth", 0) > 0 and 0 < nb < 1024:  # the sums go into the Adam launch (defer_reductions)
-        mlp.set_pending_reduce(pr)
-        _Defer.nets.append(mlp)
-        mlp.grad_write_end(cur)
-        return
-    pr.launch()
-    mlp.grad_write_end(cur)
+    _hand_over(mlp, pr, cur, defer and 0 < nb < 1024)  # (the Adam launch sums fewer than 1,024 rows)
 
 
 def _launch_bwd_multi(jobs):
@@ -484,8 +491,8 @@ def _launch_bwd_multi(jobs):
         tiles = sum((j.x2.shape[0] + 15) // 16 for j in jobs)
         n_pass = 16 * tiles
         path_pass = lib.insr_jet_bwd_path(n_pass, din, dout, L, W, cmode)
-        if (lib.insr_jet_bwd_kernel(n_pass, din, dout, L, W, cmode) == 1 and path_pass == 2) or \
-                (path_pass == 1 and L > 0):
+        # (path 3, the recompute kernel, has no multi sweep: its jobs carry no saved streams)
+        if _splits_phases(lib, path_pass, n_pass, din, dout, L, W, cmode) and path_pass != 3:
             with torch.cuda.stream(cur):
                 work = torch.empty(max(lib.insr_jet_bwd_work_bytes(n_pass, din, dout, L, W, cmode) // 4, 1),
                                    device=jobs[0].x2.device, dtype=torch.float32)
@@ -495,12 +502,7 @@ def _launch_bwd_multi(jobs):
             if rc == 0:
                 pr = PendingSums("split", work, 0, 0, (mlp, jobs[0].x2, n_pass, cmode), gflat, accumulate, cur,
                                  (mode, n_pass, W, (din, dout, L)))
-                if defer:
-                    mlp.set_pending_reduce(pr)
-                    _Defer.nets.append(mlp)
-                else:  # (the same sums now: deferred or not, the gradient is the same bits)
-                    pr.launch()
-                mlp.grad_write_end(cur)
+                _hand_over(mlp, pr, cur, defer)  # (deferred or not, the gradient is the same bits)
                 return
             if rc != -1:  # (INSR_EINVAL: not this path after all -- the calls below)
                 nat.check(rc, "insr_siren_jet_bwd_multi_sweep")
@@ -518,12 +520,7 @@ def _launch_bwd_multi(jobs):
                 stride = lib.insr_jet_partial_stride(din, dout, L, W)
                 pr = PendingSums("rows", work, nb, stride, mlp, gflat, accumulate, cur,
                                  (mode, int(sum(ns)), W, (din, dout, L)))
-                if defer and 0 < nb < 1024:
-                    mlp.set_pending_reduce(pr)
-                    _Defer.nets.append(mlp)
-                elif nb > 0:
-                    pr.launch()
-                mlp.grad_write_end(cur)
+                _hand_over(mlp, pr, cur, defer and 0 < nb < 1024, launch=nb > 0)
                 return
             # (INSR_EINVAL: a job takes another path -- the full call below)
     for k in range(0, len(jobs), nat.MAX_BWD_JOBS):

@@ -61,61 +61,6 @@ static bool knobs_ok(int mode) {
   return pol <= 6 && f <= 8;
 }
 
-// The recompute backward (jet_fb.hpp: forward + reverse jet per tile in one persistent launch, no
-// saved streams) serves W = 128 nets of 4 hidden layers at the fp32-level backward precision
-// (its products are f16x3 with per-tile scales).  The decision must not depend on n (the forward
-// of the same call skips its saved streams).  Forced by policy 4 only: measured 196 us at 16,708
-// Laplacian points vs 172 us for the two-kernel backward (kbench r4e, profiles/r04/) --
-// VALU / barrier-latency bound, see DESIGN.md.
-bool use_fb(int S, int NT, bool lap, int nq, int L, const Knobs& k) {
-  if (NT != 8 || nq != 3 || !fb_supported(S, lap, L)) return false;
-  return k.policy == 4;
-}
-
-// The resident-dW backward (jet_x6r.hpp) serves W = 128 nets of 4 hidden layers (the fluid
-// nets; compiled for that depth only) at x6 precision: value, 2-d gradient and 2-d Laplacian
-// jets.  Auto policy (8-wave blocks; kbench r3c, profiles/r03/kbench_policies.jsonl, backward
-// into .grad incl. sums): Laplacian jets from 32,768 points (33,092: 325 vs 340 us two-kernel;
-// 65,536: 544 vs 632), value jets from 49,152 (65,536: 171-177 vs 224-234; 33,092 equal;
-// 16,708: 80 vs 64-69 fused -- below ~8 tiles per CU the 64 MB of per-CU dW partials dominate).
-bool resident_ok(int S, int NT, bool lap, int nq, int L) {
-  if (NT != 8 || nq != 3) return false;
-  if (L == 5) return S == 3 && !lap;  // (the jet_fb.hpp saved-stream sweep only: jet_x6r is compiled for L = 4)
-  if (L != 4) return false;
-  return (S == 1 && !lap) || (S == 3 && !lap) || (S == 4 && lap);
-}
-// Round 3: with the two-kernel path's products on the fp16 matrix cores (INSR_BWD_F16_DW | PROP;
-// the resident kernel stays bf16x6) the two-kernel Laplacian backward wins at the fluid2DtlgnM batch
-// (66,844 points: 553-561 vs 590-601 us; value jets tie at 199-205, profiles/r03/final_r3o/
-// kbench_policy_M.jsonl), so the auto policy keeps the resident kernel for value jets only then.
-bool use_resident_f16(long n, int S, int NT, bool lap, int nq, int L, const Knobs& k);
-bool use_resident(long n, int S, int NT, bool lap, int nq, int L, const Knobs& k) {
-  if (!resident_ok(S, NT, lap, nq, L)) return false;
-  if (L == 5) return use_resident_f16(n, S, NT, lap, nq, L, k);  // no jet_x6r instantiation at this depth
-  if (k.policy == 3 || k.policy == 5) return true;
-  if (k.policy != 0) return false;
-  if (use_resident_f16(n, S, NT, lap, nq, L, k)) return true;
-  const bool f16w = (k.f16 & (INSR_BWD_F16_DW | INSR_BWD_F16_PROP)) == (INSR_BWD_F16_DW | INSR_BWD_F16_PROP);
-  return lap ? (!f16w && n >= 32768) : (S == 1 && n >= 49152);
-}
-
-// Which kernel serves the resident path: the saved-stream variant of the recompute kernel (jet_fb.hpp
-// SAVED: the reverse sweep on the forward's saved streams, f16x3 products with per-tile scales; the
-// INSR_BWD_F16_FUSED bit of the call's mask) or jet_x6r.hpp (bf16x6 products).  Policy 5 forces the
-// former.  Auto: 2-d Laplacian jets from 4,096 points -- backward into .grad incl. sums (kbench r4j,
-// profiles/r04/kbench_resident_f16.jsonl): 16,708 points 142 vs 166 us two-kernel, 33,092 239 vs
-// 296-301, 66,844 428 vs 577-582; value jets lose at every size (S = 1: 16-point tiles, 90 vs 57 fused
-// at 16,708), so they keep their paths.  Round 4, with both backwards' sums in the Adam launch: from
-// 4,096 points (the fluid2DtlgnM 8-way shard step, 8,192 + 163 points: 0.331-0.332 vs 0.345-0.347 ms
-// with the two-kernel path, profiles/r04/ab_fb_shard/).
-bool use_resident_f16(long n, int S, int NT, bool lap, int nq, int L, const Knobs& k) {
-  if (NT != 8 || nq != 3 || !fb_saved_supported(S, lap, L)) return false;
-  if (k.policy == 5) return true;
-  if (k.policy != 0 || !(k.f16 & INSR_BWD_F16_FUSED)) return false;
-  // round 6: also the 5-layer 2-d gradient jet (the el2D deformation net's Jacobian) from 4,096 points
-  return (lap && S == 4 && n >= 4096) || (!lap && S == 3 && L == 5 && n >= 4096);
-}
-
 // Matrix-core precision of the tile-split kernels (a call's INSR_JET_PREC(p) / INSR_JET_BPREC(p);
 // base.MLP(precision=...) sets them per network), else the defaults:
 //   INSR_PREC_F32     v_mfma_f32_16x16x4_f32 (jet_split.hpp)
@@ -166,6 +111,90 @@ bool use_wide(long n, int S, int NT, bool lap, int nq, const Knobs& k) {
   if (lap || S >= 3) return n >= 8192;
   return S == 1 && n >= 24576;
 }
+
+// The kernel a reverse jet runs on: the fused tile-split kernel writing partial rows (jet_bwd_x6 / jet_split),
+// the two-kernel path (jet_x6w.hpp), the resident bf16x6 kernel (jet_x6r.hpp), the saved-stream f16x3 sweep
+// (jet_fb.hpp SAVED) or the recompute kernel (jet_fb.hpp).  JetCall::bwd_kernel is the one place that chooses.
+enum class BwdKernel { Fused, Wide, ResidentX6, SweepSaved, Recompute };
+// the backward runs as a sweep into `work` and separate sums (insr_siren_jet_bwd_grad_adam phases 1 / 2)
+static bool splits_phases(BwdKernel kn, int L) {
+  return kn == BwdKernel::SweepSaved || kn == BwdKernel::Recompute || (kn == BwdKernel::Wide && L > 0);
+}
+// the backward reads the forward's saved streams (the recompute kernel reruns the forward per tile)
+static bool reads_act(BwdKernel kn) { return kn != BwdKernel::Recompute; }
+// the public answers: insr_jet_bwd_path 0..3 and insr_jet_bwd_kernel 0 / 1 (1: a jet_fb.hpp kernel)
+static int path_code(BwdKernel kn) { return kn == BwdKernel::Recompute ? 3 : kn >= BwdKernel::ResidentX6 ? 2 : (int)kn; }
+static int family_code(BwdKernel kn) { return kn >= BwdKernel::SweepSaved ? 1 : 0; }
+
+// one jet call's configuration: jet mode, streams, row tiles, bf16 terms per direction, knobs
+struct JetCall {
+  int jm, S, NT, nqf, nqb;
+  bool lap;
+  Knobs k;
+  JetCall(int din, int W, int mode)
+      : jm(mode & INSR_MODE_MASK),
+        S(streams_for(din, mode & INSR_MODE_MASK)),
+        NT(nt_for(W)),
+        nqf(nq_of(call_prec(mode, 0))),
+        nqb(nq_of(call_prec(mode, 1))),
+        lap((mode & INSR_MODE_MASK) == INSR_MODE_LAP),
+        k(knobs_of(mode)) {}
+  bool ok() const { return S > 0 && NT > 0; }
+  // the answer of insr_jet_bwd_is_wide: the two-kernel test alone, even where a persistent kernel wins
+  bool wide(long n) const { return use_wide(n, S, NT, lap, nqb, k); }
+  // precision of the fused tile-split backward: width 256 has no fused split-bf16 backward (the two-kernel
+  // path serves it), so exact fp32 serves the entries that ask for partial rows there
+  int bwd_nq() const { return NT > 8 ? 0 : nqb; }
+
+  // The backward routing policy, as one decision list: the first kernel whose conditions hold.
+  BwdKernel bwd_kernel(long n, int L) const {
+    // the three persistent kernels serve W = 128 at the fp32-level backward precision (bf16x6) only
+    if (NT == 8 && nqb == 3) {
+      // 1. The recompute backward (jet_fb.hpp: forward + reverse jet per tile in one persistent launch, no
+      // saved streams; its products are f16x3 with per-tile scales) for nets of 4 hidden layers.  The
+      // decision must not depend on n (the forward of the same call skips its saved streams).  Forced by
+      // policy 4 only: measured 196 us at 16,708 Laplacian points vs 172 us for the two-kernel backward
+      // (kbench r4e, profiles/r04/) -- VALU / barrier-latency bound, see DESIGN.md.
+      if (k.policy == 4 && fb_supported(S, lap, L)) return BwdKernel::Recompute;
+      // 2. The resident-dW backward: value, 2-d gradient and 2-d Laplacian jets of nets of 4 hidden layers
+      // (the fluid nets; jet_x6r.hpp is compiled for that depth only), and -- through the saved-stream
+      // sweep alone -- the 2-d gradient jet of 5 hidden layers.
+      const bool deep = L == 5 && S == 3 && !lap;
+      const bool fluid = L == 4 && ((S == 1 && !lap) || (S == 3 && !lap) || (S == 4 && lap));
+      if (deep || fluid) {
+        // 2a. Which kernel serves it: the saved-stream variant of the recompute kernel (jet_fb.hpp SAVED: the
+        // reverse sweep on the forward's saved streams, f16x3 products with per-tile scales; the
+        // INSR_BWD_F16_FUSED bit of the call's mask) or jet_x6r.hpp (bf16x6 products).  Policy 5 forces the
+        // former.  Auto: 2-d Laplacian jets from 4,096 points -- backward into .grad incl. sums (kbench r4j,
+        // profiles/r04/kbench_resident_f16.jsonl): 16,708 points 142 vs 166 us two-kernel, 33,092 239 vs
+        // 296-301, 66,844 428 vs 577-582; value jets lose at every size (S = 1: 16-point tiles, 90 vs 57
+        // fused at 16,708), so they keep their paths.  Round 4, with both backwards' sums in the Adam
+        // launch: from 4,096 points (the fluid2DtlgnM 8-way shard step, 8,192 + 163 points: 0.331-0.332 vs
+        // 0.345-0.347 ms with the two-kernel path, profiles/r04/ab_fb_shard/).  Round 6: also the 5-layer 2-d
+        // gradient jet (the el2D deformation net's Jacobian) from 4,096 points.
+        const bool auto_saved = k.policy == 0 && (k.f16 & INSR_BWD_F16_FUSED) && n >= 4096 && ((lap && S == 4) || deep);
+        if (fb_saved_supported(S, lap, L) && (k.policy == 5 || auto_saved)) return BwdKernel::SweepSaved;
+        // 2b. jet_x6r.hpp, forced by policy 3 (or 5 where the sweep does not apply).  There is no jet_x6r
+        // instantiation at 5 hidden layers, so policy 3 is ignored at that depth.  Auto policy (8-wave
+        // blocks; kbench r3c, profiles/r03/kbench_policies.jsonl, backward into .grad incl. sums):
+        // Laplacian jets from 32,768 points (33,092: 325 vs 340 us two-kernel; 65,536: 544 vs 632), value
+        // jets from 49,152 (65,536: 171-177 vs 224-234; 33,092 equal; 16,708: 80 vs 64-69 fused -- below
+        // ~8 tiles per CU the 64 MB of per-CU dW partials dominate).  Round 3: with the two-kernel path's
+        // products on the fp16 matrix cores (INSR_BWD_F16_DW | PROP; the resident kernel stays bf16x6) the
+        // two-kernel Laplacian backward wins at the fluid2DtlgnM batch (66,844 points: 553-561 vs 590-601
+        // us; value jets tie at 199-205, profiles/r03/final_r3o/kbench_policy_M.jsonl), so the auto policy
+        // keeps the resident kernel for value jets only then.
+        const bool f16w = (k.f16 & (INSR_BWD_F16_DW | INSR_BWD_F16_PROP)) == (INSR_BWD_F16_DW | INSR_BWD_F16_PROP);
+        const bool auto_x6r = k.policy == 0 && (lap ? (!f16w && n >= 32768) : (S == 1 && n >= 49152));
+        if (fluid && (k.policy == 3 || k.policy == 5 || auto_x6r)) return BwdKernel::ResidentX6;
+      }
+    }
+    // 3. the two-kernel path (use_wide above), 4. the fused tile-split kernel
+    return wide(n) ? BwdKernel::Wide : BwdKernel::Fused;
+  }
+  // the one choice that never depends on n (a multi-job call asks it once for all of its jobs)
+  bool recomputes(int L) const { return bwd_kernel(0, L) == BwdKernel::Recompute; }
+};
 
 static int cu_count() { return device_cus(); }
 
@@ -593,65 +622,6 @@ bool shape_ok(int din, int dout, int L, int width, int mode) {
   return true;
 }
 
-// one jet call's configuration: jet mode, streams, row tiles, bf16 terms per direction, knobs
-struct JetCall {
-  int jm, S, NT, nqf, nqb;
-  bool lap;
-  Knobs k;
-  JetCall(int din, int W, int mode)
-      : jm(mode & INSR_MODE_MASK),
-        S(streams_for(din, mode & INSR_MODE_MASK)),
-        NT(nt_for(W)),
-        nqf(nq_of(call_prec(mode, 0))),
-        nqb(nq_of(call_prec(mode, 1))),
-        lap((mode & INSR_MODE_MASK) == INSR_MODE_LAP),
-        k(knobs_of(mode)) {}
-  bool ok() const { return S > 0 && NT > 0; }
-  // width 256 has no fused split-bf16 backward: the two-kernel path serves it
-  bool wide(long n) const { return use_wide(n, S, NT, lap, nqb, k); }
-  bool resident(long n, int L) const { return use_resident(n, S, NT, lap, nqb, L, k); }
-  bool recompute(int L) const { return use_fb(S, NT, lap, nqb, L, k); }
-  bool resident_f16(long n, int L) const { return resident(n, L) && use_resident_f16(n, S, NT, lap, nqb, L, k); }
-  // 0: fused tile-split + partial rows (insr_siren_jet_bwd), 1: two-kernel, 2: resident dW,
-  // 3: recompute (no saved streams)
-  int path(long n, int L) const { return recompute(L) ? 3 : (resident(n, L) ? 2 : (wide(n) ? 1 : 0)); }
-};
-
-}  // namespace insr
-
-using namespace insr;
-
-extern "C" {
-
-int insr_version(void) { return 300; }
-
-long insr_siren_param_count(int din, int dout, int L, int W) {
-  return (long)W * din + W + (long)L * ((long)W * W + W) + (long)dout * W + dout;
-}
-
-long insr_jet_partial_stride(int din, int dout, int L, int W) {
-  return (insr_siren_param_count(din, dout, L, W) + 3) & ~3L;  // 16-B aligned rows
-}
-
-// ---- pre-split weight planes --------------------------------------------------------------
-long insr_siren_wsplit_offset(int din, int dout, int L, int W) {
-  if (!shape_ok(din, dout, L, W, 0)) return INSR_EINVAL;
-  return wsplit_offset(din, dout, L, W);
-}
-long insr_siren_wsplit_floats(int L, int W) {
-  if (L < 0 || nt_for(W) < 0) return INSR_EINVAL;
-  return wsplit_total_floats(L, W);
-}
-int insr_siren_wsplit(float* params, int din, int dout, int L, int W, void* stream) {
-  if (!params || !shape_ok(din, dout, L, W, 0)) return INSR_EINVAL;
-  return wsplit_launch(params, din, dout, L, W, params + wsplit_offset(din, dout, L, W), (hipStream_t)stream);
-}
-
-int insr_split_f16(const float* in, unsigned* hi, unsigned* lo, long npairs, void* stream) {
-  if (npairs < 0 || npairs > (1L << 31) || (npairs && (!in || !hi || !lo))) return INSR_EINVAL;
-  return split_f16_probe_launch(in, hi, lo, npairs, (hipStream_t)stream);
-}
-
 // A call without INSR_MODE_WSPLIT whose kernels read weight planes: a per-(device, stream,
 // slot) scratch [copy of the parameters | planes] is filled (one copy + one split launch) and
 // used as the params buffer.  Allocation happens outside stream capture only.
@@ -694,6 +664,314 @@ static const float* with_planes(const float* params, int din, int dout, int L, i
   if ((*rc = (int)hipMemcpyAsync(buf, params, (size_t)pc * sizeof(float), hipMemcpyDeviceToDevice, st))) return nullptr;
   if ((*rc = wsplit_launch(buf, din, dout, L, W, buf + wsplit_offset(din, dout, L, W), st))) return nullptr;
   return buf;
+}
+
+// InsrBwdJob[] -> the job table of the two-kernel and jet_fb.hpp backwards: the live jobs in order, job m's
+// tiles at [tstart[m], tstart[m + 1]).  act = false: the recompute kernel's table (act is not read)
+static FbJobs fb_jobs(const InsrBwdJob* jobs, int njobs, bool act = true) {
+  FbJobs J{};
+  int m = 0, t = 0;
+  for (int k = 0; k < njobs; ++k) {
+    if (jobs[k].n <= 0) continue;
+    J.x[m] = jobs[k].x;
+    J.act[m] = act ? jobs[k].act : nullptr;
+    J.gy[m] = jobs[k].gy;
+    J.gdy[m] = jobs[k].gdy;
+    J.glap[m] = jobs[k].glap;
+    J.n[m] = (int)jobs[k].n;
+    J.tstart[m] = t;
+    t += (int)((jobs[k].n + 15) / 16);
+    ++m;
+  }
+  J.tstart[m] = t;
+  J.njobs = m;
+  return J;
+}
+static FbJobs fb_jobs(const float* x, long n, const float* act, const float* gy, const float* gdy, const float* glap) {
+  const InsrBwdJob j{x, act, gy, gdy, glap, n};
+  return fb_jobs(&j, 1);
+}
+
+// InsrBwdJob[] -> the job table of the fused tile-split backward: jobs pick[0..nj) (NULL: 0..nj), job q on
+// blocks [first[q], first[q + 1]) = blocks[q] of them, nbal[q] > 0: a balanced shape's block count
+static BwdJobsX6 x6_jobs(const InsrBwdJob* jobs, const int* pick, int nj, const int* blocks, const int* nbal) {
+  BwdJobsX6 J{};
+  int b = 0;
+  for (int q = 0; q < nj; ++q) {
+    const InsrBwdJob& jb = jobs[pick ? pick[q] : q];
+    J.x[q] = jb.x;
+    J.act[q] = jb.act;
+    J.gy[q] = jb.gy;
+    J.gdy[q] = jb.gdy;
+    J.glap[q] = jb.glap;
+    J.n[q] = (int)jb.n;
+    J.nbal[q] = nbal[q];
+    J.first[q] = b;
+    b += blocks[q];
+  }
+  J.first[nj] = b;
+  J.njobs = nj;
+  return J;
+}
+static BwdJobsX6 x6_jobs(const float* x, long n, const float* act, const float* gy, const float* gdy, const float* glap,
+                         int blocks, int nbal) {
+  const InsrBwdJob j{x, act, gy, gdy, glap, n};
+  return x6_jobs(&j, nullptr, 1, &blocks, &nbal);
+}
+
+// blocks of the fused tile-split backward of n points (insr_jet_partial_blocks)
+static int fused_blocks(const LaunchShape& sh, long n) {
+  return sh.nbal > 0 ? sh.nbal : (int)(((n + 15) / 16 + sh.T - 1) / sh.T);
+}
+
+// The fused tile-split backward of one call: partial-gradient rows into `partial`
+static int bwd_fused_impl(const float* x, long n, int din, int dout, int L, int W, int mode, const float* params,
+                          const float* act, const float* gy, const float* gdy, const float* glap, float* partial,
+                          const SeedTab* seeds, void* stream) {
+  if (!shape_ok(din, dout, L, W, mode) || n < 0 || n > 0x7fffffffL) return INSR_EINVAL;
+  if (n == 0) return 0;
+  if (!x || !params || !act || !partial) return INSR_EINVAL;
+  const JetCall c(din, W, mode);
+  const long P = insr_jet_partial_stride(din, dout, L, W);  // row stride of the partial rows
+  const int nq = c.bwd_nq();
+  const LaunchShape sh = launch_shape(1, nq, c.NT, c.S, c.lap, n, c.k);
+  int rc = 0;
+  if (nq > 0 && !(params = with_planes(params, din, dout, L, W, mode, (hipStream_t)stream, 0, &rc))) return rc;
+  BwdJobsX6 J = x6_jobs(x, n, act, gy, gdy, glap, fused_blocks(sh, n), sh.nbal);
+  if (seeds) {
+    if (nq == 0) return INSR_EINVAL;  // the exact-fp32 kernel takes no seeds
+    J.seeds = *seeds;
+  }
+  return bwd_q(fused_bwd_nq(nq, c.k), c.NT, c.S, c.lap, sh.T, &J, din, dout, L, params, partial, P, (hipStream_t)stream);
+}
+
+// Plan of a multi-job backward (insr_siren_jet_bwd_grad_multi): the jobs whose own size takes the
+// fused tile-split path share one launch, T from the launch shape of their combined batch; a
+// balanced shape (T = 3 / 5) gives each job its share of the balanced block count (never fewer
+// blocks than T-tile blocks need); every other job runs alone on its own path.
+namespace {
+struct MultiPlan {
+  int nq, T, nf, ns, nb;
+  int fused[kBwdJobs], solo[kBwdJobs], blocks[kBwdJobs], nbal[kBwdJobs];
+};
+}  // namespace
+
+static int plan_multi(const long* n, int njobs, int din, int dout, int L, int W, int mode, MultiPlan& p) {
+  if (!n || njobs < 1 || njobs > kBwdJobs || !shape_ok(din, dout, L, W, mode)) return INSR_EINVAL;
+  const JetCall c(din, W, mode);
+  p = MultiPlan{};
+  p.nq = c.bwd_nq();
+  long total = 0, tiles = 0;
+  for (int k = 0; k < njobs; ++k) {
+    if (n[k] < 0 || n[k] > 0x7fffffffL) return INSR_EINVAL;
+    if (n[k] == 0) continue;
+    if (p.nq > 0 && c.bwd_kernel(n[k], L) == BwdKernel::Fused) {
+      p.fused[p.nf++] = k;
+      total += n[k];
+      tiles += (n[k] + 15) / 16;
+    } else {
+      p.solo[p.ns++] = k;
+    }
+  }
+  if (total > 0x7fffffffL) return INSR_EINVAL;
+  if (p.nf == 0) return 0;
+  const LaunchShape sh = launch_shape(1, p.nq, c.NT, c.S, c.lap, total, c.k);
+  p.T = sh.T;
+  for (int q = 0; q < p.nf; ++q) {
+    const long tk = (n[p.fused[q]] + 15) / 16, plain = (tk + sh.T - 1) / sh.T;
+    long nbk = plain;
+    if (sh.nbal > 0) {
+      const long share = (tk * sh.nbal + tiles / 2) / tiles;
+      nbk = share > plain ? share : plain;
+    }
+    p.blocks[q] = (int)nbk;
+    p.nbal[q] = sh.nbal > 0 ? (int)nbk : 0;
+    p.nb += (int)nbk;
+  }
+  return 0;
+}
+
+// the multi plan's fused tile-split jobs in ONE jet_bwd_x6 launch: p.nb partial-gradient rows into work
+static int multi_fused_rows(const InsrBwdJob* jobs, const MultiPlan& p, int din, int dout, int L, int W, int mode,
+                            const float* params, float* work, hipStream_t st) {
+  const JetCall c(din, W, mode);
+  int rc = 0;
+  if (!(params = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
+  const BwdJobsX6 J = x6_jobs(jobs, p.fused, p.nf, p.blocks, p.nbal);
+  const long P = insr_jet_partial_stride(din, dout, L, W);
+  return bwd_q(fused_bwd_nq(p.nq, c.k), c.NT, c.S, c.lap, p.T, &J, din, dout, L, params, work, P, st);
+}
+
+// The two-kernel (wide) backward of a job table laid out over N points (jet_x6w.hpp wide_bwd_t): phases /
+// Adam epilogue as wide_bwd_t
+static int wide_bwd_jobs(const JetCall& c, const FbJobs& J, long N, int din, int dout, int L, int W, int mode,
+                         const float* params, float* work, float* grad, int accumulate, int phases, const AdamArgs& A,
+                         hipStream_t st) {
+  int rc = 0;
+  if (!(params = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
+  switch (c.nqb) {
+    case 3: return dispatch_wide_bwd_q<3>(c.NT, c.S, c.lap, J, (int)N, din, dout, L, params, work, grad, accumulate, c.k.f16, phases, A, st);
+    case 2: return dispatch_wide_bwd_q<2>(c.NT, c.S, c.lap, J, (int)N, din, dout, L, params, work, grad, accumulate, c.k.f16, phases, A, st);
+    default: return dispatch_wide_bwd_q<1>(c.NT, c.S, c.lap, J, (int)N, din, dout, L, params, work, grad, accumulate, c.k.f16, phases, A, st);
+  }
+}
+
+// The single-job call of the jet_fb.hpp backward (kn: the recompute kernel, or the resident sweep on the
+// saved streams): phases / Adam epilogue as fb_bwd_t
+static int fb_bwd_call(const JetCall& c, BwdKernel kn, const float* x, long n, int din, int dout, int L, int W, int mode,
+                       const float* params, const float* act, const float* gy, const float* gdy, const float* glap,
+                       float* work, float* grad, int accumulate, int phases, const AdamArgs& A, hipStream_t st,
+                       const SeedTab* seeds = nullptr) {
+  int rc = 0;
+  if (!(params = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
+  FbJobs J = fb_jobs(x, n, reads_act(kn) ? act : nullptr, gy, gdy, glap);
+  if (seeds) J.seeds = *seeds;
+  return dispatch_fb_bwd(c.S, c.lap, L, J, din, dout, params, work, grad, accumulate, reads_act(kn) ? 1 : 0, phases,
+                         A, st);
+}
+
+// InsrLossFin -> the device descriptor (NULL: none)
+static int fin_of(const InsrLossFin* f, LossFin& F) {
+  F = LossFin{};
+  if (!f) return 0;
+  if (!f->part || f->rows < 1 || f->nloss < 1 || f->nloss > INSR_SEED_MAX) return INSR_EINVAL;
+  F.part = f->part;
+  F.rows = f->rows;
+  F.nloss = f->nloss;
+  for (int k = 0; k < f->nloss; ++k) {
+    if (!f->out[k]) return INSR_EINVAL;
+    F.scale[k] = f->scale[k];
+    F.out[k] = f->out[k];
+  }
+  return 0;
+}
+
+// InsrSeed[] -> the device table of a one-job launch (job 0); rejects a seeded stream whose adjoint
+// pointer is set, overlapping terms of one stream, and malformed terms
+static int seeds_of(const InsrSeed* seeds, int ns, float* lpart, const float* gy, const float* gdy, const float* glap,
+                    SeedTab& T) {
+  T = SeedTab{};
+  if (!seeds || ns < 1 || ns > INSR_SEED_MAX || !lpart) return INSR_EINVAL;
+  for (int k = 0; k < ns; ++k) {
+    const InsrSeed& q = seeds[k];
+    if (!q.a || q.n < 0 || q.a_off < 0 || q.loss < 0 || q.loss >= INSR_SEED_MAX) return INSR_EINVAL;
+    if (q.stream < INSR_SEED_VALUE || q.stream > INSR_SEED_LAP) return INSR_EINVAL;
+    if ((q.stream == INSR_SEED_VALUE && gy) || (q.stream == INSR_SEED_GRAD && gdy) || (q.stream == INSR_SEED_LAP && glap))
+      return INSR_EINVAL;
+    if (q.kind == INSR_LOSS_COMBO) {
+      if ((q.d && !q.c) || q.sb < 1 || q.sc < 1 || q.sd < 1) return INSR_EINVAL;
+    } else if (q.kind == INSR_LOSS_BANDS) {
+      if (q.m < 2 || q.b || q.c || q.d || q.a_off % q.m) return INSR_EINVAL;
+    } else {
+      return INSR_EINVAL;
+    }
+    const long hi = q.a_off + (q.kind == INSR_LOSS_COMBO ? q.n : 2 * q.n * q.m);
+    for (int j = 0; j < k; ++j) {
+      const InsrSeed& o = seeds[j];
+      const long ohi = o.a_off + (o.kind == INSR_LOSS_COMBO ? o.n : 2 * o.n * o.m);
+      if (o.stream == q.stream && q.a_off < ohi && o.a_off < hi) return INSR_EINVAL;
+    }
+    SeedTerm& t = T.t[k];
+    t.a = q.a + q.a_off;
+    t.b = q.b;
+    t.c = q.c;
+    t.d = q.d;
+    t.alpha = q.alpha;
+    t.beta = q.beta;
+    t.gamma = q.gamma;
+    t.delta = q.delta;
+    t.sb = q.sb;
+    t.sc = q.sc;
+    t.sd = q.sd;
+    t.n = q.n;
+    t.a_off = q.a_off;
+    t.g2 = 2.f * q.scale;
+    t.kind = q.kind;
+    t.m = q.m;
+    t.job = 0;
+    t.stream = q.stream;
+    t.loss = q.loss;
+  }
+  T.nt = ns;
+  T.lpart = lpart;
+  return 0;
+}
+
+// insr_siren_jet_bwd_grad in two halves, for the kernels that split (splits_phases): phases 1 = the sweep
+// into `work`, 2 = the sums (with the Adam update when exp_avg is set, and the seeded losses' finish), 3 = both
+static int grad_adam_impl(const float* x, long n, int din, int dout, int L, int W, int mode, float* params,
+                          const float* act, const float* gy, const float* gdy, const float* glap, float* work,
+                          float* grad, int accumulate, int phases, float* exp_avg, float* exp_avg_sq, float* opt_state,
+                          float beta1, float beta2, float eps, const float* loss, int patience, const LossFin& fin,
+                          const SeedTab* seeds, void* stream) {
+  if (!shape_ok(din, dout, L, W, mode) || n < 1 || n > 0x7fffffffL || phases < 1 || phases > 3) return INSR_EINVAL;
+  const JetCall c(din, W, mode);
+  const BwdKernel kn = c.bwd_kernel(n, L);
+  if (!splits_phases(kn, L)) return INSR_EINVAL;
+  if (!params || !work || !grad) return INSR_EINVAL;
+  if ((phases & 1) && (!x || (!act && reads_act(kn)))) return INSR_EINVAL;  // the sweep's inputs
+  AdamArgs A;
+  if ((phases & 2) && exp_avg) {
+    if (!exp_avg_sq || !opt_state) return INSR_EINVAL;
+    A.p = params;
+    A.m = exp_avg;
+    A.v = exp_avg_sq;
+    A.st = opt_state;
+    A.loss = loss;
+    A.patience = patience;
+    A.b1 = beta1;
+    A.b2 = beta2;
+    A.eps = eps;
+    if (mode & INSR_MODE_WSPLIT) {  // the buffer carries the weight planes: the update rewrites them
+      A.shape[0] = din;
+      A.shape[1] = dout;
+      A.shape[2] = L;
+      A.shape[3] = W;
+    }
+  }
+  A.fin = fin;
+  // seeds and their losses' finish: the saved-stream sweep only
+  if ((fin.nloss && !(phases & 2)) || ((seeds || fin.nloss) && kn != BwdKernel::SweepSaved)) return INSR_EINVAL;
+  if (kn == BwdKernel::Wide)
+    return wide_bwd_jobs(c, fb_jobs(x, n, act, gy, gdy, glap), n, din, dout, L, W, mode, params, work, grad, accumulate,
+                         phases, A, (hipStream_t)stream);
+  return fb_bwd_call(c, kn, x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, grad, accumulate, phases, A,
+                     (hipStream_t)stream, seeds);
+}
+
+}  // namespace insr
+
+using namespace insr;
+
+extern "C" {
+
+int insr_version(void) { return 300; }
+
+long insr_siren_param_count(int din, int dout, int L, int W) {
+  return (long)W * din + W + (long)L * ((long)W * W + W) + (long)dout * W + dout;
+}
+
+long insr_jet_partial_stride(int din, int dout, int L, int W) {
+  return (insr_siren_param_count(din, dout, L, W) + 3) & ~3L;  // 16-B aligned rows
+}
+
+// ---- pre-split weight planes --------------------------------------------------------------
+long insr_siren_wsplit_offset(int din, int dout, int L, int W) {
+  if (!shape_ok(din, dout, L, W, 0)) return INSR_EINVAL;
+  return wsplit_offset(din, dout, L, W);
+}
+long insr_siren_wsplit_floats(int L, int W) {
+  if (L < 0 || nt_for(W) < 0) return INSR_EINVAL;
+  return wsplit_total_floats(L, W);
+}
+int insr_siren_wsplit(float* params, int din, int dout, int L, int W, void* stream) {
+  if (!params || !shape_ok(din, dout, L, W, 0)) return INSR_EINVAL;
+  return wsplit_launch(params, din, dout, L, W, params + wsplit_offset(din, dout, L, W), (hipStream_t)stream);
+}
+
+int insr_split_f16(const float* in, unsigned* hi, unsigned* lo, long npairs, void* stream) {
+  if (npairs < 0 || npairs > (1L << 31) || (npairs && (!in || !hi || !lo))) return INSR_EINVAL;
+  return split_f16_probe_launch(in, hi, lo, npairs, (hipStream_t)stream);
 }
 
 int insr_siren_wsplit_status(const float* params, int din, int dout, int L, int W, void* stream) {
@@ -902,94 +1180,163 @@ int insr_siren_jet_fwd_mixed(const InsrJetJob* jobs, const int* modes, const flo
   return 0;
 }
 
-static int bwd_fused_impl(const float* x, long n, int din, int dout, int L, int W, int mode, const float* params,
-                          const float* act, const float* gy, const float* gdy, const float* glap, float* partial,
-                          const SeedTab* seeds, void* stream) {
-  if (!shape_ok(din, dout, L, W, mode) || n < 0 || n > 0x7fffffffL) return INSR_EINVAL;
-  if (n == 0) return 0;
-  if (!x || !params || !act || !partial) return INSR_EINVAL;
+// ---- reverse jets: host queries ---------------------------------------------------------------
+int insr_jet_partial_blocks(long n, int din, int W, int mode) {
   const JetCall c(din, W, mode);
-  const long P = insr_jet_partial_stride(din, dout, L, W);  // row stride of the partial rows
-  // width 256: the fused split-bf16 backward does not exist -- exact fp32 serves this entry
-  const int nq = c.NT > 8 ? 0 : c.nqb;
-  const LaunchShape sh = launch_shape(1, nq, c.NT, c.S, c.lap, n, c.k);
-  int rc = 0;
-  if (nq > 0 && !(params = with_planes(params, din, dout, L, W, mode, (hipStream_t)stream, 0, &rc))) return rc;
-  BwdJobsX6 J{};
-  J.x[0] = x;
-  J.act[0] = act;
-  J.gy[0] = gy;
-  J.gdy[0] = gdy;
-  J.glap[0] = glap;
-  J.n[0] = (int)n;
-  J.nbal[0] = sh.nbal;
-  J.first[0] = 0;
-  J.first[1] = sh.nbal > 0 ? sh.nbal : (int)(((n + 15) / 16 + sh.T - 1) / sh.T);
-  J.njobs = 1;
-  if (seeds) {
-    if (nq == 0) return INSR_EINVAL;  // the exact-fp32 kernel takes no seeds
-    J.seeds = *seeds;
-  }
-  return bwd_q(fused_bwd_nq(nq, c.k), c.NT, c.S, c.lap, sh.T, &J, din, dout, L, params, partial, P, (hipStream_t)stream);
+  if (!c.ok() || n < 0) return INSR_EINVAL;
+  if (n == 0) return 0;
+  return fused_blocks(launch_shape(1, c.bwd_nq(), c.NT, c.S, c.lap, n, c.k), n);
 }
 
+int insr_jet_split_tiles(long n, int din, int W, int mode, int backward) {
+  const JetCall c(din, W, mode);
+  if (!c.ok() || n < 0) return INSR_EINVAL;
+  return launch_shape(backward ? 1 : 0, backward ? c.bwd_nq() : c.nqf, c.NT, c.S, c.lap, n, c.k).T;
+}
+
+// (the two-kernel test alone, even where a persistent kernel wins: tests/test_gpu_fullsize.py relies on it)
+int insr_jet_bwd_is_wide(long n, int din, int W, int mode) {
+  const JetCall c(din, W, mode);
+  if (!c.ok() || n < 0) return INSR_EINVAL;
+  return c.wide(n) ? 1 : 0;
+}
+
+// (answers 1 for a net without hidden layers too, where the split-phase entries refuse the two-kernel
+// path -- splits_phases -- and insr_siren_jet_bwd_grad alone runs it)
+int insr_jet_bwd_path(long n, int din, int dout, int L, int W, int mode) {
+  if (!shape_ok(din, dout, L, W, mode) || n < 0) return INSR_EINVAL;
+  return path_code(JetCall(din, W, mode).bwd_kernel(n, L));
+}
+
+int insr_jet_bwd_kernel(long n, int din, int dout, int L, int W, int mode) {
+  if (!shape_ok(din, dout, L, W, mode) || n < 0) return INSR_EINVAL;
+  return family_code(JetCall(din, W, mode).bwd_kernel(n, L));
+}
+
+long insr_jet_bwd_work_bytes(long n, int din, int dout, int L, int W, int mode) {
+  if (!shape_ok(din, dout, L, W, mode) || n < 0) return INSR_EINVAL;
+  const JetCall c(din, W, mode);
+  switch (c.bwd_kernel(n, L)) {
+    case BwdKernel::Recompute:
+    case BwdKernel::SweepSaved: return fb_work_floats((n + 15) / 16, din, dout, L) * (long)sizeof(float);
+    case BwdKernel::ResidentX6: return resident_work_floats(n, din, dout, L) * (long)sizeof(float);
+    case BwdKernel::Wide: return wide_work_floats(n, din, dout, L, W, c.S) * (long)sizeof(float);
+    case BwdKernel::Fused: break;
+  }
+  return insr_jet_partial_bytes(n, din, dout, L, W, mode);
+}
+
+int insr_jet_wide_launch_threads(long n, int din, int dout, int L, int W, int mode, long* threads3) {
+  if (!shape_ok(din, dout, L, W, mode) || n <= 0 || !threads3 || L < 1) return INSR_EINVAL;
+  const JetCall c(din, W, mode);
+  const BwdKernel kn = c.bwd_kernel(n, L);
+  switch (kn) {
+    case BwdKernel::Fused: return INSR_EINVAL;
+    case BwdKernel::Wide: wide_launch_threads(n, din, dout, L, W, c.S, threads3); return 0;
+    default: break;
+  }
+  // the persistent launch + the dW / compact-row sums
+  const long Ps = (long)W * din + W + (long)L * W + (long)dout * W + dout;
+  const long wq = ((long)W * W / 4 + 63) / 64, rows_x = (Ps + 63) / 64;
+  threads3[0] = (long)(kn == BwdKernel::ResidentX6 ? resident_blocks(n) : fb_launch_blocks((n + 15) / 16)) * 512;
+  threads3[1] = (wq > rows_x ? wq : rows_x) * (L + 1) * 512;
+  threads3[2] = 0;
+  return 0;
+}
+
+int insr_jet_bwd_seed_rows(long n, int din, int dout, int L, int W, int mode) {
+  if (!shape_ok(din, dout, L, W, mode) || n < 0 || n > 0x7fffffffL) return INSR_EINVAL;
+  if (n == 0) return 0;
+  const JetCall c(din, W, mode);
+  switch (c.bwd_kernel(n, L)) {
+    case BwdKernel::Fused:  // the fused tile-split kernel stages seeds for value jets (jet_x6.hpp jet_bwd_x6, S = 1)
+      return (c.S == 1 && c.bwd_nq() > 0) ? insr_jet_partial_blocks(n, din, W, mode) : 0;
+    case BwdKernel::SweepSaved: {  // jet_fb.hpp on the saved streams: its tiles per block staged in LDS
+      const long tiles = (n + 15) / 16, nb = fb_launch_blocks(tiles);
+      return (tiles + nb - 1) / nb <= kFbSeedTiles ? (int)nb : 0;
+    }
+    default: return 0;
+  }
+}
+
+// ---- reverse jets: one call -------------------------------------------------------------------
 int insr_siren_jet_bwd(const float* x, long n, int din, int dout, int L, int W, int mode, const float* params,
                        const float* act, const float* gy, const float* gdy, const float* glap, float* partial,
                        void* stream) {
   return bwd_fused_impl(x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, partial, nullptr, stream);
 }
 
-// Plan of a multi-job backward (insr_siren_jet_bwd_grad_multi): the jobs whose own size takes the
-// fused tile-split path share one launch, T from the launch shape of their combined batch; a
-// balanced shape (T = 3 / 5) gives each job its share of the balanced block count (never fewer
-// blocks than T-tile blocks need); every other job runs alone on its own path.
-namespace {
-struct MultiPlan {
-  int nq, T, nf, ns, nb;
-  int fused[kBwdJobs], solo[kBwdJobs], blocks[kBwdJobs], nbal[kBwdJobs];
-};
-}  // namespace
-
-static int plan_multi(const long* n, int njobs, int din, int dout, int L, int W, int mode, MultiPlan& p) {
-  if (!n || njobs < 1 || njobs > kBwdJobs || !shape_ok(din, dout, L, W, mode)) return INSR_EINVAL;
+int insr_siren_jet_bwd_grad(const float* x, long n, int din, int dout, int L, int W, int mode, const float* params,
+                            const float* act, const float* gy, const float* gdy, const float* glap, float* work,
+                            float* grad, int accumulate, void* stream) {
+  if (!shape_ok(din, dout, L, W, mode) || n < 0 || n > 0x7fffffffL) return INSR_EINVAL;
+  if (n == 0) return 0;
   const JetCall c(din, W, mode);
-  p = MultiPlan{};
-  p.nq = c.NT > 8 ? 0 : c.nqb;
-  long total = 0, tiles = 0;
-  for (int k = 0; k < njobs; ++k) {
-    if (n[k] < 0 || n[k] > 0x7fffffffL) return INSR_EINVAL;
-    if (n[k] == 0) continue;
-    if (p.nq > 0 && c.path(n[k], L) == 0) {
-      p.fused[p.nf++] = k;
-      total += n[k];
-      tiles += (n[k] + 15) / 16;
-    } else {
-      p.solo[p.ns++] = k;
-    }
+  const BwdKernel kn = c.bwd_kernel(n, L);
+  if (!x || !params || (!act && reads_act(kn)) || !work || !grad) return INSR_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = 0;
+  switch (kn) {
+    case BwdKernel::Recompute:
+    case BwdKernel::SweepSaved:
+      return fb_bwd_call(c, kn, x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, grad, accumulate, 3,
+                         AdamArgs{}, st);
+    case BwdKernel::ResidentX6:
+      if (!(params = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
+      return dispatch_resident_bwd(c.S, c.lap, L, x, (int)n, din, dout, params, act, gy, gdy, glap, work, grad,
+                                   accumulate, st);
+    case BwdKernel::Wide:
+      return wide_bwd_jobs(c, fb_jobs(x, n, act, gy, gdy, glap), n, din, dout, L, W, mode, params, work, grad,
+                           accumulate, 3, AdamArgs{}, st);
+    case BwdKernel::Fused: break;
   }
-  if (total > 0x7fffffffL) return INSR_EINVAL;
-  if (p.nf == 0) return 0;
-  const LaunchShape sh = launch_shape(1, p.nq, c.NT, c.S, c.lap, total, c.k);
-  p.T = sh.T;
-  for (int q = 0; q < p.nf; ++q) {
-    const long tk = (n[p.fused[q]] + 15) / 16, plain = (tk + sh.T - 1) / sh.T;
-    long nbk = plain;
-    if (sh.nbal > 0) {
-      const long share = (tk * sh.nbal + tiles / 2) / tiles;
-      nbk = share > plain ? share : plain;
-    }
-    p.blocks[q] = (int)nbk;
-    p.nbal[q] = sh.nbal > 0 ? (int)nbk : 0;
-    p.nb += (int)nbk;
-  }
-  return 0;
+  if ((rc = insr_siren_jet_bwd(x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, stream))) return rc;
+  return insr_reduce_partials_strided(work, insr_jet_partial_blocks(n, din, W, mode),
+                                      insr_siren_param_count(din, dout, L, W), insr_jet_partial_stride(din, dout, L, W),
+                                      grad, accumulate, stream);
 }
 
+int insr_siren_jet_bwd_grad_adam(const float* x, long n, int din, int dout, int L, int W, int mode, float* params,
+                                 const float* act, const float* gy, const float* gdy, const float* glap, float* work,
+                                 float* grad, int accumulate, int phases, float* exp_avg, float* exp_avg_sq,
+                                 float* opt_state, float beta1, float beta2, float eps, const float* loss, int patience,
+                                 void* stream) {
+  return grad_adam_impl(x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, grad, accumulate, phases,
+                        exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, loss, patience, LossFin{}, nullptr, stream);
+}
+
+int insr_siren_jet_bwd_grad_adam_fin(const float* x, long n, int din, int dout, int L, int W, int mode, float* params,
+                                     float* work, float* grad, int accumulate, float* exp_avg, float* exp_avg_sq,
+                                     float* opt_state, float beta1, float beta2, float eps, const float* loss,
+                                     int patience, const InsrLossFin* fin, void* stream) {
+  LossFin F;
+  if (fin_of(fin, F)) return INSR_EINVAL;
+  return grad_adam_impl(x, n, din, dout, L, W, mode, params, nullptr, nullptr, nullptr, nullptr, work, grad,
+                        accumulate, 2, exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, loss, patience, F, nullptr,
+                        stream);
+}
+
+int insr_siren_jet_bwd_seeded(const float* x, long n, int din, int dout, int L, int W, int mode, const float* params,
+                              const float* act, const float* gy, const float* gdy, const float* glap,
+                              const InsrSeed* seeds, int n_seeds, float* loss_part, float* work, void* stream) {
+  if (insr_jet_bwd_seed_rows(n, din, dout, L, W, mode) <= 0) return INSR_EINVAL;
+  SeedTab T;
+  if (seeds_of(seeds, n_seeds, loss_part, gy, gdy, glap, T)) return INSR_EINVAL;
+  if (!x || !params || !act || !work) return INSR_EINVAL;
+  switch (JetCall(din, W, mode).bwd_kernel(n, L)) {  // (seed rows > 0: one of these two)
+    case BwdKernel::SweepSaved:  // the jet_fb sweep (phase 1); phase 2: insr_siren_jet_bwd_grad_adam_fin
+      return grad_adam_impl(x, n, din, dout, L, W, mode, const_cast<float*>(params), act, gy, gdy, glap, work, work, 0,
+                            1, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, 0, LossFin{}, &T, stream);
+    default: return bwd_fused_impl(x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, &T, stream);
+  }
+}
+
+// ---- reverse jets: several calls of one network -------------------------------------------------
 long insr_jet_bwd_multi_work_bytes(const long* n, int njobs, int din, int dout, int L, int W, int mode) {
   MultiPlan p;
   const int rc = plan_multi(n, njobs, din, dout, L, W, mode, p);
   if (rc) return rc;
-  if (JetCall(din, W, mode).recompute(L)) {
+  if (JetCall(din, W, mode).recomputes(L)) {
     long tiles = 0;
     for (int k = 0; k < njobs; ++k) tiles += n[k] > 0 ? (n[k] + 15) / 16 : 0;
     return fb_work_floats(tiles, din, dout, L) * (long)sizeof(float);
@@ -1003,17 +1350,11 @@ long insr_jet_bwd_multi_work_bytes(const long* n, int njobs, int din, int dout, 
   return bytes;
 }
 
-static int wide_bwd_jobs(const JetCall& c, const FbJobs& J, long N, int din, int dout, int L, int W, int mode,
-                         const float* params, float* work, float* grad, int accumulate, int phases, const AdamArgs& A,
-                         hipStream_t st);
-static int multi_fused_rows(const InsrBwdJob* jobs, const MultiPlan& p, int din, int dout, int L, int W, int mode,
-                            const float* params, float* work, hipStream_t st);
-
 int insr_siren_jet_bwd_grad_multi(const InsrBwdJob* jobs, int njobs, int din, int dout, int L, int W, int mode,
                                   const float* params, float* work, float* grad, int accumulate, void* stream) {
   if (!jobs || njobs < 1 || njobs > kBwdJobs) return INSR_EINVAL;
   long ns[kBwdJobs];
-  const bool fb = shape_ok(din, dout, L, W, mode) && JetCall(din, W, mode).recompute(L);
+  const bool fb = shape_ok(din, dout, L, W, mode) && JetCall(din, W, mode).recomputes(L);
   for (int k = 0; k < njobs; ++k) {
     ns[k] = jobs[k].n;
     if (jobs[k].n > 0 && (!jobs[k].x || (!jobs[k].act && !fb))) return INSR_EINVAL;
@@ -1025,28 +1366,11 @@ int insr_siren_jet_bwd_grad_multi(const InsrBwdJob* jobs, int njobs, int din, in
   if (!params || !work || !grad) return INSR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   int acc = accumulate ? 1 : 0;
-  {
+  if (fb) {  // every job in ONE recompute launch (act is not read)
     const JetCall c(din, W, mode);
-    if (c.recompute(L)) {  // every job in ONE recompute launch (act is not read)
-      FbJobs J{};
-      int m = 0, t = 0;
-      for (int k = 0; k < njobs; ++k) {
-        if (jobs[k].n <= 0) continue;
-        J.x[m] = jobs[k].x;
-        J.gy[m] = jobs[k].gy;
-        J.gdy[m] = jobs[k].gdy;
-        J.glap[m] = jobs[k].glap;
-        J.n[m] = (int)jobs[k].n;
-        J.tstart[m] = t;
-        t += (int)((jobs[k].n + 15) / 16);
-        ++m;
-      }
-      J.tstart[m] = t;
-      J.njobs = m;
-      const float* prm = params;
-      if (!(prm = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
-      return dispatch_fb_bwd(c.S, c.lap, L, J, din, dout, prm, work, grad, acc, 0, 3, AdamArgs{}, st);
-    }
+    if (!(params = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
+    return dispatch_fb_bwd(c.S, c.lap, L, fb_jobs(jobs, njobs, false), din, dout, params, work, grad, acc, 0, 3,
+                           AdamArgs{}, st);
   }
   if (p.nf > 0) {
     if ((rc = multi_fused_rows(jobs, p, din, dout, L, W, mode, params, work, st))) return rc;
@@ -1076,7 +1400,7 @@ int insr_siren_jet_bwd_multi_rows(const InsrBwdJob* jobs, int njobs, int din, in
   MultiPlan p;
   int rc = plan_multi(ns, njobs, din, dout, L, W, mode, p);
   if (rc) return rc;
-  if (p.ns > 0 || JetCall(din, W, mode).recompute(L)) return INSR_EINVAL;  // a job another path serves
+  if (p.ns > 0 || JetCall(din, W, mode).recomputes(L)) return INSR_EINVAL;  // a job another path serves
   if (p.nf == 0) return 0;
   if (!params || !work) return INSR_EINVAL;
   if ((rc = multi_fused_rows(jobs, p, din, dout, L, W, mode, params, work, (hipStream_t)stream))) return rc;
@@ -1094,363 +1418,26 @@ int insr_siren_jet_bwd_multi_sweep(const InsrBwdJob* jobs, int njobs, int din, i
     total += jobs[k].n;
     tiles += (jobs[k].n + 15) / 16;
   }
-  // the saved-stream resident sweep (jet_fb.hpp, f16x3) or -- round 6 -- the two-kernel backward (jet_x6w.hpp,
-  // e.g. elasticity's interior batch + constraint bands, elasticity/model.py:137,161-174) must be the path of the
-  // jobs' total; the two-kernel jobs are laid out over npass = 16 x their tiles, and phase 2 (the sums, with the
-  // Adam launch: insr_siren_jet_bwd_grad_adam phases 2 at n = npass) finds them there
+  // the saved-stream resident sweep (jet_fb.hpp, f16x3) must be the kernel of the jobs' total, or -- round 6 --
+  // the two-kernel backward (jet_x6w.hpp, e.g. elasticity's interior batch + constraint bands,
+  // elasticity/model.py:137,161-174) that of npass = 16 x their tiles: the two-kernel jobs are laid out over npass
+  // points, and phase 2 (the sums, with the Adam launch: insr_siren_jet_bwd_grad_adam phases 2 at n = npass)
+  // finds them there.  (The two tests ask at different sizes: total for the sweep, npass for the two-kernel path.)
   const long npass = 16 * tiles;
-  const bool fbp = !c.recompute(L) && c.resident(total, L) && c.resident_f16(total, L);
-  const bool widep = !fbp && !c.recompute(L) && L > 0 && !c.resident(npass, L) && c.wide(npass);
-  if (total > 0x7fffffffL || npass > 0x7fffffffL || !(fbp || widep)) return INSR_EINVAL;
+  const bool sweep = c.bwd_kernel(total, L) == BwdKernel::SweepSaved;
+  const bool wide = !sweep && L > 0 && c.bwd_kernel(npass, L) == BwdKernel::Wide;
+  if (total > 0x7fffffffL || npass > 0x7fffffffL || !(sweep || wide)) return INSR_EINVAL;
   if (tiles == 0) return 0;
   if (!params || !work) return INSR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  int rc = 0;
-  const float* prm = params;
-  if (!(prm = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
-  FbJobs J{};
-  int m = 0, t = 0;
-  for (int k = 0; k < njobs; ++k) {
-    if (jobs[k].n <= 0) continue;
-    J.x[m] = jobs[k].x;
-    J.act[m] = jobs[k].act;
-    J.gy[m] = jobs[k].gy;
-    J.gdy[m] = jobs[k].gdy;
-    J.glap[m] = jobs[k].glap;
-    J.n[m] = (int)jobs[k].n;
-    J.tstart[m] = t;
-    t += (int)((jobs[k].n + 15) / 16);
-    ++m;
-  }
-  J.tstart[m] = t;
-  J.njobs = m;
-  if (widep) return wide_bwd_jobs(c, J, npass, din, dout, L, W, mode, params, work, nullptr, 0, 1, AdamArgs{}, st);
-  return dispatch_fb_bwd(c.S, c.lap, L, J, din, dout, prm, work, nullptr, 0, 1, 1, AdamArgs{}, st);
-}
-
-// the multi plan's fused tile-split jobs in ONE jet_bwd_x6 launch: p.nb partial-gradient rows into work
-static int multi_fused_rows(const InsrBwdJob* jobs, const MultiPlan& p, int din, int dout, int L, int W, int mode,
-                            const float* params, float* work, hipStream_t st) {
-  int rc = 0;
-  {
-    const JetCall c(din, W, mode);
-    const float* prm = params;
-    if (!(prm = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
-    BwdJobsX6 J{};
-    int b = 0;
-    for (int q = 0; q < p.nf; ++q) {
-      const InsrBwdJob& jb = jobs[p.fused[q]];
-      J.x[q] = jb.x;
-      J.act[q] = jb.act;
-      J.gy[q] = jb.gy;
-      J.gdy[q] = jb.gdy;
-      J.glap[q] = jb.glap;
-      J.n[q] = (int)jb.n;
-      J.nbal[q] = p.nbal[q];
-      J.first[q] = b;
-      b += p.blocks[q];
-    }
-    J.first[p.nf] = b;
-    J.njobs = p.nf;
-    const long P = insr_jet_partial_stride(din, dout, L, W);
-    return bwd_q(fused_bwd_nq(p.nq, c.k), c.NT, c.S, c.lap, p.T, &J, din, dout, L, prm, work, P, st);
-  }
-}
-
-long insr_jet_bwd_work_bytes(long n, int din, int dout, int L, int W, int mode) {
-  if (!shape_ok(din, dout, L, W, mode) || n < 0) return INSR_EINVAL;
-  const JetCall c(din, W, mode);
-  if (c.recompute(L) || c.resident_f16(n, L)) return fb_work_floats((n + 15) / 16, din, dout, L) * (long)sizeof(float);
-  if (c.resident(n, L)) return resident_work_floats(n, din, dout, L) * (long)sizeof(float);
-  if (c.wide(n)) return wide_work_floats(n, din, dout, L, W, c.S) * (long)sizeof(float);
-  return insr_jet_partial_bytes(n, din, dout, L, W, mode);
-}
-
-int insr_jet_wide_launch_threads(long n, int din, int dout, int L, int W, int mode, long* threads3) {
-  if (!shape_ok(din, dout, L, W, mode) || n <= 0 || !threads3 || L < 1) return INSR_EINVAL;
-  const JetCall c(din, W, mode);
-  if (c.recompute(L) || c.resident(n, L)) {  // the persistent launch + the dW / compact-row sums
-    const long Ps = (long)W * din + W + (long)L * W + (long)dout * W + dout;
-    const long wq = ((long)W * W / 4 + 63) / 64, rows_x = (Ps + 63) / 64;
-    threads3[0] = (long)((c.recompute(L) || c.resident_f16(n, L)) ? fb_launch_blocks((n + 15) / 16) : resident_blocks(n)) * 512;
-    threads3[1] = (wq > rows_x ? wq : rows_x) * (L + 1) * 512;
-    threads3[2] = 0;
-    return 0;
-  }
-  if (!c.wide(n)) return INSR_EINVAL;
-  wide_launch_threads(n, din, dout, L, W, c.S, threads3);
-  return 0;
-}
-
-int insr_jet_bwd_is_wide(long n, int din, int W, int mode) {
-  const JetCall c(din, W, mode);
-  if (!c.ok() || n < 0) return INSR_EINVAL;
-  return c.wide(n) ? 1 : 0;
-}
-
-int insr_jet_bwd_path(long n, int din, int dout, int L, int W, int mode) {
-  if (!shape_ok(din, dout, L, W, mode) || n < 0) return INSR_EINVAL;
-  return JetCall(din, W, mode).path(n, L);
-}
-
-int insr_jet_bwd_kernel(long n, int din, int dout, int L, int W, int mode) {
-  if (!shape_ok(din, dout, L, W, mode) || n < 0) return INSR_EINVAL;
-  const JetCall c(din, W, mode);
-  const int p = c.path(n, L);
-  return (p == 3 || (p == 2 && c.resident_f16(n, L))) ? 1 : 0;
-}
-
-// The two-kernel (wide) backward of a job table laid out over N points (jet_x6w.hpp wide_bwd_t)
-static int wide_bwd_jobs(const JetCall& c, const FbJobs& J, long N, int din, int dout, int L, int W, int mode,
-                         const float* params, float* work, float* grad, int accumulate, int phases, const AdamArgs& A,
-                         hipStream_t st) {
+  const FbJobs J = fb_jobs(jobs, njobs);
+  if (wide) return wide_bwd_jobs(c, J, npass, din, dout, L, W, mode, params, work, nullptr, 0, 1, AdamArgs{}, st);
   int rc = 0;
   if (!(params = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
-  switch (c.nqb) {
-    case 3: return dispatch_wide_bwd_q<3>(c.NT, c.S, c.lap, J, (int)N, din, dout, L, params, work, grad, accumulate, c.k.f16, phases, A, st);
-    case 2: return dispatch_wide_bwd_q<2>(c.NT, c.S, c.lap, J, (int)N, din, dout, L, params, work, grad, accumulate, c.k.f16, phases, A, st);
-    default: return dispatch_wide_bwd_q<1>(c.NT, c.S, c.lap, J, (int)N, din, dout, L, params, work, grad, accumulate, c.k.f16, phases, A, st);
-  }
+  return dispatch_fb_bwd(c.S, c.lap, L, J, din, dout, params, work, nullptr, 0, 1, 1, AdamArgs{}, st);
 }
 
-// The two-kernel (wide) backward of one call: phases / Adam epilogue as wide_bwd_t
-static int wide_bwd_call(const JetCall& c, const float* x, long n, int din, int dout, int L, int W, int mode,
-                         const float* params, const float* act, const float* gy, const float* gdy, const float* glap,
-                         float* work, float* grad, int accumulate, int phases, const AdamArgs& A, hipStream_t st) {
-  FbJobs J{};
-  J.x[0] = x;
-  J.act[0] = act;
-  J.gy[0] = gy;
-  J.gdy[0] = gdy;
-  J.glap[0] = glap;
-  J.n[0] = (int)n;
-  J.tstart[0] = 0;
-  J.tstart[1] = (int)((n + 15) / 16);
-  J.njobs = 1;
-  return wide_bwd_jobs(c, J, n, din, dout, L, W, mode, params, work, grad, accumulate, phases, A, st);
-}
-
-// The single-job call of the jet_fb.hpp backward (the recompute kernel, or the resident sweep on the
-// saved streams): phases / Adam epilogue as fb_bwd_t
-static int fb_bwd_call(const JetCall& c, const float* x, long n, int din, int dout, int L, int W, int mode,
-                       const float* params, const float* act, const float* gy, const float* gdy, const float* glap,
-                       float* work, float* grad, int accumulate, int phases, const AdamArgs& A, hipStream_t st,
-                       const SeedTab* seeds = nullptr) {
-  int rc = 0;
-  if (!(params = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
-  FbJobs J{};
-  if (seeds) J.seeds = *seeds;
-  J.x[0] = x;
-  J.act[0] = c.recompute(L) ? nullptr : act;
-  J.gy[0] = gy;
-  J.gdy[0] = gdy;
-  J.glap[0] = glap;
-  J.n[0] = (int)n;
-  J.tstart[0] = 0;
-  J.tstart[1] = (int)((n + 15) / 16);
-  J.njobs = 1;
-  return dispatch_fb_bwd(c.S, c.lap, L, J, din, dout, params, work, grad, accumulate, c.recompute(L) ? 0 : 1, phases,
-                         A, st);
-}
-
-// InsrLossFin -> the device descriptor (NULL: none)
-static int fin_of(const InsrLossFin* f, LossFin& F) {
-  F = LossFin{};
-  if (!f) return 0;
-  if (!f->part || f->rows < 1 || f->nloss < 1 || f->nloss > INSR_SEED_MAX) return INSR_EINVAL;
-  F.part = f->part;
-  F.rows = f->rows;
-  F.nloss = f->nloss;
-  for (int k = 0; k < f->nloss; ++k) {
-    if (!f->out[k]) return INSR_EINVAL;
-    F.scale[k] = f->scale[k];
-    F.out[k] = f->out[k];
-  }
-  return 0;
-}
-
-static int grad_adam_impl(const float* x, long n, int din, int dout, int L, int W, int mode, float* params,
-                          const float* act, const float* gy, const float* gdy, const float* glap, float* work,
-                          float* grad, int accumulate, int phases, float* exp_avg, float* exp_avg_sq, float* opt_state,
-                          float beta1, float beta2, float eps, const float* loss, int patience, const LossFin& fin,
-                          const SeedTab* seeds, void* stream) {
-  if (!shape_ok(din, dout, L, W, mode) || n < 1 || n > 0x7fffffffL || phases < 1 || phases > 3) return INSR_EINVAL;
-  const JetCall c(din, W, mode);
-  const bool fb = c.recompute(L) || (c.resident(n, L) && c.resident_f16(n, L));  // jet_fb.hpp's backward
-  const bool wide = !fb && !c.resident(n, L) && c.wide(n) && L > 0;               // the two-kernel backward
-  if (!fb && !wide) return INSR_EINVAL;
-  if (!params || !work || !grad) return INSR_EINVAL;
-  if ((phases & 1) && (!x || (!act && !c.recompute(L)))) return INSR_EINVAL;  // the sweep's inputs
-  AdamArgs A;
-  if ((phases & 2) && exp_avg) {
-    if (!exp_avg_sq || !opt_state) return INSR_EINVAL;
-    A.p = params;
-    A.m = exp_avg;
-    A.v = exp_avg_sq;
-    A.st = opt_state;
-    A.loss = loss;
-    A.patience = patience;
-    A.b1 = beta1;
-    A.b2 = beta2;
-    A.eps = eps;
-    if (mode & INSR_MODE_WSPLIT) {  // the buffer carries the weight planes: the update rewrites them
-      A.shape[0] = din;
-      A.shape[1] = dout;
-      A.shape[2] = L;
-      A.shape[3] = W;
-    }
-  }
-  A.fin = fin;
-  if ((fin.nloss && !(phases & 2)) || ((seeds || fin.nloss) && (wide || c.recompute(L)))) return INSR_EINVAL;
-  if (wide)
-    return wide_bwd_call(c, x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, grad, accumulate, phases,
-                         A, (hipStream_t)stream);
-  return fb_bwd_call(c, x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, grad, accumulate, phases, A,
-                     (hipStream_t)stream, seeds);
-}
-
-int insr_siren_jet_bwd_grad_adam(const float* x, long n, int din, int dout, int L, int W, int mode, float* params,
-                                 const float* act, const float* gy, const float* gdy, const float* glap, float* work,
-                                 float* grad, int accumulate, int phases, float* exp_avg, float* exp_avg_sq,
-                                 float* opt_state, float beta1, float beta2, float eps, const float* loss, int patience,
-                                 void* stream) {
-  return grad_adam_impl(x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, grad, accumulate, phases,
-                        exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, loss, patience, LossFin{}, nullptr, stream);
-}
-
-int insr_siren_jet_bwd_grad_adam_fin(const float* x, long n, int din, int dout, int L, int W, int mode, float* params,
-                                     float* work, float* grad, int accumulate, float* exp_avg, float* exp_avg_sq,
-                                     float* opt_state, float beta1, float beta2, float eps, const float* loss,
-                                     int patience, const InsrLossFin* fin, void* stream) {
-  LossFin F;
-  if (fin_of(fin, F)) return INSR_EINVAL;
-  return grad_adam_impl(x, n, din, dout, L, W, mode, params, nullptr, nullptr, nullptr, nullptr, work, grad,
-                        accumulate, 2, exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, loss, patience, F, nullptr,
-                        stream);
-}
-
-// InsrSeed[] -> the device table of a one-job launch (job 0); rejects a seeded stream whose adjoint
-// pointer is set, overlapping terms of one stream, and malformed terms
-static int seeds_of(const InsrSeed* seeds, int ns, float* lpart, const float* gy, const float* gdy, const float* glap,
-                    SeedTab& T) {
-  T = SeedTab{};
-  if (!seeds || ns < 1 || ns > INSR_SEED_MAX || !lpart) return INSR_EINVAL;
-  for (int k = 0; k < ns; ++k) {
-    const InsrSeed& q = seeds[k];
-    if (!q.a || q.n < 0 || q.a_off < 0 || q.loss < 0 || q.loss >= INSR_SEED_MAX) return INSR_EINVAL;
-    if (q.stream < INSR_SEED_VALUE || q.stream > INSR_SEED_LAP) return INSR_EINVAL;
-    if ((q.stream == INSR_SEED_VALUE && gy) || (q.stream == INSR_SEED_GRAD && gdy) || (q.stream == INSR_SEED_LAP && glap))
-      return INSR_EINVAL;
-    if (q.kind == INSR_LOSS_COMBO) {
-      if ((q.d && !q.c) || q.sb < 1 || q.sc < 1 || q.sd < 1) return INSR_EINVAL;
-    } else if (q.kind == INSR_LOSS_BANDS) {
-      if (q.m < 2 || q.b || q.c || q.d || q.a_off % q.m) return INSR_EINVAL;
-    } else {
-      return INSR_EINVAL;
-    }
-    const long hi = q.a_off + (q.kind == INSR_LOSS_COMBO ? q.n : 2 * q.n * q.m);
-    for (int j = 0; j < k; ++j) {
-      const InsrSeed& o = seeds[j];
-      const long ohi = o.a_off + (o.kind == INSR_LOSS_COMBO ? o.n : 2 * o.n * o.m);
-      if (o.stream == q.stream && q.a_off < ohi && o.a_off < hi) return INSR_EINVAL;
-    }
-    SeedTerm& t = T.t[k];
-    t.a = q.a + q.a_off;
-    t.b = q.b;
-    t.c = q.c;
-    t.d = q.d;
-    t.alpha = q.alpha;
-    t.beta = q.beta;
-    t.gamma = q.gamma;
-    t.delta = q.delta;
-    t.sb = q.sb;
-    t.sc = q.sc;
-    t.sd = q.sd;
-    t.n = q.n;
-    t.a_off = q.a_off;
-    t.g2 = 2.f * q.scale;
-    t.kind = q.kind;
-    t.m = q.m;
-    t.job = 0;
-    t.stream = q.stream;
-    t.loss = q.loss;
-  }
-  T.nt = ns;
-  T.lpart = lpart;
-  return 0;
-}
-
-int insr_jet_bwd_seed_rows(long n, int din, int dout, int L, int W, int mode) {
-  if (!shape_ok(din, dout, L, W, mode) || n < 0 || n > 0x7fffffffL) return INSR_EINVAL;
-  if (n == 0) return 0;
-  const JetCall c(din, W, mode);
-  const int p = c.path(n, L);
-  // the fused tile-split kernel stages seeds for value jets (jet_x6.hpp jet_bwd_x6, S = 1)
-  if (p == 0) return (c.S == 1 && (c.NT > 8 ? 0 : c.nqb) > 0) ? insr_jet_partial_blocks(n, din, W, mode) : 0;
-  if (p == 2 && c.resident_f16(n, L)) {  // jet_fb.hpp on the saved streams: its tiles per block staged in LDS
-    const long tiles = (n + 15) / 16, nb = fb_launch_blocks(tiles);
-    return (tiles + nb - 1) / nb <= kFbSeedTiles ? (int)nb : 0;
-  }
-  return 0;
-}
-
-int insr_siren_jet_bwd_seeded(const float* x, long n, int din, int dout, int L, int W, int mode, const float* params,
-                              const float* act, const float* gy, const float* gdy, const float* glap,
-                              const InsrSeed* seeds, int n_seeds, float* loss_part, float* work, void* stream) {
-  if (insr_jet_bwd_seed_rows(n, din, dout, L, W, mode) <= 0) return INSR_EINVAL;
-  SeedTab T;
-  if (seeds_of(seeds, n_seeds, loss_part, gy, gdy, glap, T)) return INSR_EINVAL;
-  if (!x || !params || !act || !work) return INSR_EINVAL;
-  const JetCall c(din, W, mode);
-  if (c.path(n, L) == 2)  // the jet_fb sweep (phase 1); phase 2: insr_siren_jet_bwd_grad_adam_fin
-    return grad_adam_impl(x, n, din, dout, L, W, mode, const_cast<float*>(params), act, gy, gdy, glap, work, work, 0, 1,
-                          nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, 0, LossFin{}, &T, stream);
-  return bwd_fused_impl(x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, &T, stream);
-}
-
-int insr_siren_jet_bwd_grad(const float* x, long n, int din, int dout, int L, int W, int mode, const float* params,
-                            const float* act, const float* gy, const float* gdy, const float* glap, float* work,
-                            float* grad, int accumulate, void* stream) {
-  if (!shape_ok(din, dout, L, W, mode) || n < 0 || n > 0x7fffffffL) return INSR_EINVAL;
-  if (n == 0) return 0;
-  const JetCall c(din, W, mode);
-  if (!x || !params || (!act && !c.recompute(L)) || !work || !grad) return INSR_EINVAL;
-  if (c.recompute(L) || (c.resident(n, L) && c.resident_f16(n, L)))  // jet_fb.hpp: one job
-    return fb_bwd_call(c, x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, grad, accumulate, 3,
-                       AdamArgs{}, (hipStream_t)stream);
-  if (c.resident(n, L)) {
-    hipStream_t st = (hipStream_t)stream;
-    int rc = 0;
-    if (!(params = with_planes(params, din, dout, L, W, mode, st, 0, &rc))) return rc;
-    return dispatch_resident_bwd(c.S, c.lap, L, x, (int)n, din, dout, params, act, gy, gdy, glap, work, grad,
-                                 accumulate, st);
-  }
-  if (c.wide(n))
-    return wide_bwd_call(c, x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, grad, accumulate, 3,
-                         AdamArgs{}, (hipStream_t)stream);
-  int rc = insr_siren_jet_bwd(x, n, din, dout, L, W, mode, params, act, gy, gdy, glap, work, stream);
-  if (rc) return rc;
-  return insr_reduce_partials_strided(work, insr_jet_partial_blocks(n, din, W, mode),
-                                      insr_siren_param_count(din, dout, L, W), insr_jet_partial_stride(din, dout, L, W),
-                                      grad, accumulate, stream);
-}
-
-int insr_jet_partial_blocks(long n, int din, int W, int mode) {
-  const JetCall c(din, W, mode);
-  if (!c.ok() || n < 0) return INSR_EINVAL;
-  if (n == 0) return 0;
-  const int nq = c.NT > 8 ? 0 : c.nqb;
-  const LaunchShape sh = launch_shape(1, nq, c.NT, c.S, c.lap, n, c.k);
-  return sh.nbal > 0 ? sh.nbal : (int)(((n + 15) / 16 + sh.T - 1) / sh.T);
-}
-
-int insr_jet_split_tiles(long n, int din, int W, int mode, int backward) {
-  const JetCall c(din, W, mode);
-  if (!c.ok() || n < 0) return INSR_EINVAL;
-  const int nq = backward ? (c.NT > 8 ? 0 : c.nqb) : c.nqf;
-  return launch_shape(backward ? 1 : 0, nq, c.NT, c.S, c.lap, n, c.k).T;
-}
-
+// ---- partial-row sums and the device-resident optimiser -----------------------------------------
 static int reduce_partials_impl(const float* partial, int nb, long count, long stride, float* grad, int accumulate,
                                 const LossFin& fin, void* stream) {
   if (!partial || !grad || nb < 0 || count < 0 || stride < count) return INSR_EINVAL;

@@ -232,6 +232,75 @@ def test_backward_path_policy(lib):
     assert lib.insr_jet_bwd_path(16708, 2, 1, 4, 128, LAP | (9 << nat.MODE_F16_SHIFT)) == -1
 
 
+def test_backward_routing_answers_agree(lib):
+    """Every routing query answers from one choice of the backward kernel (capi.hip JetCall::bwd_kernel), so
+    the answers are consistent with each other -- over a thinned grid of tools/route_table.py's arguments."""
+    import ctypes
+    import itertools
+    from base import _native as nat
+    shapes = [(2, 1, 4, 128), (2, 2, 4, 128), (2, 2, 5, 128), (1, 1, 4, 128), (3, 3, 4, 128), (2, 1, 3, 128),
+              (2, 1, 0, 128), (2, 2, 4, 64), (1, 1, 3, 32), (3, 3, 5, 256), (2, 2, 0, 256)]
+    ns = [0, 1, 17, 4095, 4096, 8192, 16708, 24576, 32768, 49152, 66844]
+    knobs = [nat.jet_policy(p) | f | w for p in range(6) for f in (0, nat.jet_bwd_f16(0), nat.jet_bwd_f16(3))
+             for w in (0, nat.MODE_WIDE128)]
+    t3 = (ctypes.c_long * 3)()
+    seen = set()
+    for (din, dout, L, W), jm, kb in itertools.product(shapes, (nat.MODE_VALUE, nat.MODE_GRAD, nat.MODE_LAP), knobs):
+        mode = jm | kb
+        recompute = set()
+        for n in ns:
+            a = (n, din, dout, L, W, mode)
+            path, kernel = lib.insr_jet_bwd_path(*a), lib.insr_jet_bwd_kernel(*a)
+            assert 0 <= path <= 3 and kernel in (0, 1), a
+            seen.add((path, kernel))
+            recompute.add(path == 3)
+            if kernel == 1:
+                assert path in (2, 3), a
+            if path == 0:
+                assert lib.insr_jet_bwd_work_bytes(*a) == lib.insr_jet_partial_bytes(*a), a
+            if path == 1:
+                assert lib.insr_jet_bwd_is_wide(n, din, W, mode) == 1, a
+            if lib.insr_jet_bwd_seed_rows(*a) > 0:
+                assert (path == 0 and jm == nat.MODE_VALUE) or (path == 2 and kernel == 1), a
+            if n > 0 and L >= 1:
+                assert (lib.insr_jet_wide_launch_threads(*a, t3) == 0) == (path >= 1), a
+        assert len(recompute) == 1, (din, dout, L, W, mode)  # path 3 never depends on n
+    assert seen == {(0, 0), (1, 0), (2, 0), (2, 1), (3, 1)}  # the grid reaches all five kernels
+
+
+def test_backward_entry_points_refuse_other_kernels(lib):
+    """The refused cells of the entry point x kernel matrix: an entry point asked for a
+    kernel it does not serve answers INSR_EINVAL before it reads a pointer (all NULL here; the job tables carry
+    dummy addresses that are never dereferenced)."""
+    from base import _native as nat
+    sh, n = (2, 1, 4, 128), 65
+    LAP, V, P = nat.MODE_LAP, nat.MODE_VALUE, nat.jet_policy
+    mode = {"fused": LAP | P(1), "wide": LAP | P(2), "x6r": LAP | P(3), "recompute": LAP | P(4), "sweep": LAP | P(5)}
+    answers = {k: (lib.insr_jet_bwd_path(n, *sh, m), lib.insr_jet_bwd_kernel(n, *sh, m)) for k, m in mode.items()}
+    assert answers == {"fused": (0, 0), "wide": (1, 0), "x6r": (2, 0), "recompute": (3, 1), "sweep": (2, 1)}
+    jobs = (nat.BwdJob * 2)(nat.BwdJob(0x10000, 0x20000, None, None, None, n),
+                            nat.BwdJob(0x30000, 0x40000, None, None, None, 17))
+
+    def grad_adam(m, phases):
+        return lib.insr_siren_jet_bwd_grad_adam(None, n, *sh, m, None, None, None, None, None, None, None, 0, phases,
+                                                None, None, None, 0.9, 0.999, 1e-8, None, 0, None)
+
+    for k in ("fused", "x6r"):  # no sweep + sums split on these kernels
+        for phases in (1, 2, 3):
+            assert grad_adam(mode[k], phases) == -1, (k, phases)
+        assert lib.insr_siren_jet_bwd_grad_adam_fin(None, n, *sh, mode[k], None, None, None, 0, None, None, None, 0.9,
+                                                    0.999, 1e-8, None, 0, None, None) == -1, k
+    assert lib.insr_jet_bwd_seed_rows(n, *sh, V) > 0 and lib.insr_jet_bwd_seed_rows(n, *sh, mode["sweep"]) > 0
+    for k in ("fused", "wide", "x6r", "recompute"):  # in-kernel seeds: fused value jets and the saved-stream sweep
+        assert lib.insr_jet_bwd_seed_rows(n, *sh, mode[k]) == 0, k
+        assert lib.insr_siren_jet_bwd_seeded(None, n, *sh, mode[k], None, None, None, None, None, None, 1, None, None,
+                                             None) == -1, k
+    for k in ("wide", "x6r", "recompute", "sweep"):  # partial rows come from the fused kernel alone
+        assert lib.insr_siren_jet_bwd_multi_rows(jobs, 2, *sh, mode[k], None, None, None) == -1, k
+    for k in ("fused", "x6r", "recompute"):  # one sweep for several calls: the saved-stream sweep, the two-kernel path
+        assert lib.insr_siren_jet_bwd_multi_sweep(jobs, 2, *sh, mode[k], None, None, None) == -1, k
+
+
 def test_multi_backward_plan(lib):
     """insr_siren_jet_bwd_grad_multi's plan, answered on the host: the value jobs of one
     network's loss.backward() -- the fluid interior (16,384 points) and its two 162-point wall
