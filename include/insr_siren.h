@@ -720,6 +720,41 @@ int insr_advect1d_iteration(const float* params, const float* prev_params, int n
                             float* points, float* partials, long stride, float* loss_part, float* losses,
                             void* stream);
 
+/*
+ * Second-order jets: the value, the Jacobian and the FULL Hessian of a d_in = 2 or 3 SIREN in one
+ * forward launch, every parameter gradient in one reverse launch (csrc/jet_hess.hpp).  The jet carries
+ * S = 1 + d + d (d + 1) / 2 streams (6 / 10): value, tangents, and one second-order stream per pair
+ * i <= j in row-major upper-triangle order.  Exact fp32 products whatever precision the network's other
+ * jets run at; no `mode` argument (no precision or knob bits).
+ *
+ *   insr_siren_hess_supported  1 where a kernel is compiled: d_in 2 / 3, d_out 1..3, width 32 / 64 / 128
+ *                              (host only; callers keep their present route where it answers 0).
+ *   insr_hess_act_bytes        the saved streams: the layout of insr_jet_act_bytes with this jet's S.
+ *   insr_hess_partial_blocks   rows of the partial-gradient buffer (one 16-point tile per block) of
+ *   insr_hess_partial_bytes    insr_jet_partial_stride(...) floats each.
+ *   insr_siren_hess_fwd        y (n, d_out), dy (n, d_out, d_in), hess (n, d_out, d_in, d_in) with both
+ *                              triangles written; act NULL = nothing saved (inference).
+ *   insr_siren_hess_bwd        adjoints gy / gdy / ghess of those shapes (any may be NULL = zero; ghess
+ *                              is a full (d_in, d_in) adjoint, folded onto the pairs at load: g_ii, and
+ *                              g_ij + g_ji) -> one partial-gradient row per block, summed by
+ *                              insr_reduce_partials_strided or insr_adam_step_partials as the rows of
+ *                              insr_siren_jet_bwd are.
+ * n == 0 returns 0 without a launch; a bad shape, n > 2^31 - 16 or a NULL required pointer returns
+ * INSR_EINVAL (a width outside the compiled set: INSR_EWIDTH) before anything touches the device.
+ * Replaces: hessian (base/diff_ops.py:6-30: d_out (1 + d_in) create_graph autograd passes) and, with the
+ * Jacobian it carries, the g, H of laplace(normalize=True) (base/diff_ops.py:33-41), plus
+ * loss.backward() through those graphs (base/baseModel.py:77).
+ */
+int insr_siren_hess_supported(int d_in, int d_out, int num_hidden, int width);
+long insr_hess_act_bytes(long n_points, int d_in, int num_hidden, int width);
+int insr_hess_partial_blocks(long n_points, int d_in, int width);
+long insr_hess_partial_bytes(long n_points, int d_in, int d_out, int num_hidden, int width);
+int insr_siren_hess_fwd(const float* x, long n_points, int d_in, int d_out, int num_hidden, int width,
+                        const float* params, float* y, float* dy, float* hess, float* act, void* stream);
+int insr_siren_hess_bwd(const float* x, long n_points, int d_in, int d_out, int num_hidden, int width,
+                        const float* params, const float* act, const float* gy, const float* gdy,
+                        const float* ghess, float* partial, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,12 @@ SIGNATURES = {
     "insr_adam_step_partials_fin": (_I, [_P, _I, _L, _P, _I, _P, _P, _P, _L, _P, _P, _F, _F, _F, _P, _I, _P, _P]),
     "insr_siren_jet_bwd_grad_adam_fin": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _F, _F, _F, _P,
                                               _I, _P, _P]),
+    "insr_siren_hess_supported": (_I, [_I, _I, _I, _I]),
+    "insr_hess_act_bytes": (_L, [_L, _I, _I, _I]),
+    "insr_hess_partial_blocks": (_I, [_L, _I, _I]),
+    "insr_hess_partial_bytes": (_L, [_L, _I, _I, _I, _I]),
+    "insr_siren_hess_fwd": (_I, [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "insr_siren_hess_bwd": (_I, [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 

@@ -12,7 +12,9 @@ base/_jet.py) and assembles the requested quantity from its streams:
   laplace    :33-41  div(grad y)           sum_c Lap y_c              (LAP jet, d_in <= 3)
   hessian    :6-30   (.., dy, dx, dx)      d_in = 1: the Laplacian stream; d_in = 2: Laplacian
                                            jets of the field and of f(x + s v) for three
-                                           directions v (polarisation), d_in <= 2
+                                           directions v (polarisation), d_in <= 2; a network
+                                           with hessian_jet=True: ONE second-order jet
+                                           (base/_hess.py), d_in = 2 and 3
 
 All results stay differentiable w.r.t. the network parameters (loss.backward()
 runs the HIP reverse jet).  `status` is returned, never raised (-1 on NaN).
@@ -31,6 +33,7 @@ import warnings
 
 import torch
 
+from . import _hess
 from . import _jet
 from . import _native as nat
 from . import lower as _lower
@@ -44,6 +47,7 @@ from .networks import MLP
 __all__ = ["hessian", "laplace", "divergence", "gradient", "jacobian"]
 
 FALLBACKS = {}  # op name -> calls served by the reference-semantics route
+HESS_JETS = {}  # op name -> calls served by the second-order jet (networks with hessian_jet=True)
 
 
 def _fallback(opname, why):
@@ -253,7 +257,31 @@ def _laplace_normalized(y, x, eps, return_grad):
         return _laplace_normalized_now(y, x, eps, return_grad)
 
 
+def _hess_route(y, x, opname):
+    """(mlp, holder, affine) when ONE second-order jet serves this call: a fused SIREN output of a
+    d_in = 2 / 3 network that opted in (MLP.hessian_jet) with a compiled kernel, outside fused_forwards
+    scopes; else None (the present routes)."""
+    r = _resolve(y, x, opname)
+    if r is None or r[0] == "gradient-of" or _jet._Fused.pending is not None or not _hess.enabled(r[0]):
+        return None
+    HESS_JETS[opname] = HESS_JETS.get(opname, 0) + 1
+    return r
+
+
 def _laplace_normalized_now(y, x, eps, return_grad):
+    r = _hess_route(y, x, "laplace")
+    if r is not None:  # g, H and tr H of sum_c y_c from the one jet
+        mlp, value, affine = r
+        _, J, Hc = _hess.hess_jet_of(mlp, value, x)
+        g = J.squeeze(-2) if J.shape[-2] == 1 else J.sum(dim=-2)
+        if affine:
+            g = g + 1.0
+        H = Hc.squeeze(-3) if Hc.shape[-3] == 1 else Hc.sum(dim=-3)
+        gn = g.norm(dim=-1, keepdim=True)
+        gHg = torch.einsum("...i,...ij,...j->...", g, H, g).unsqueeze(-1)
+        tr = torch.diagonal(H, dim1=-2, dim2=-1).sum(dim=-1, keepdim=True)
+        div = tr / (gn + eps) - gHg / (gn * (gn + eps) ** 2)
+        return (div, g / (gn + eps)) if return_grad else div
     g = gradient(y, x)
     try:
         H = _hessian_core(y, x, "laplace(normalize=True)").sum(dim=-3)  # Hessian of sum_c y_c
@@ -332,6 +360,9 @@ def _hessian_core(y, x, opname):
     if _jet._Fused.pending is not None:
         raise _jet.UnsupportedPattern(f"{opname} inside a fused_forwards scope (its jets' values are read at once)")
     d = mlp.in_features
+    if _hess.enabled(mlp):  # the network opted in: ONE second-order jet (d_in = 2, 3)
+        HESS_JETS[opname] = HESS_JETS.get(opname, 0) + 1
+        return _hess.hess_jet_of(mlp, value, x)[2]
     if d > 2:
         raise _jet.UnsupportedPattern(f"{opname}: Hessians of d_in = {d} inputs (d_in <= 2: the augmented "
                                       "Laplacian jet of f(x + s v) has d_in + 1 <= 3 inputs)")
@@ -357,7 +388,8 @@ def hessian(y, x):
     """base/diff_ops.py:6-30: y (meta, obs, channels), x (meta, obs, dim) -> the Hessian
     (meta, obs, channels, dim, dim) and status (-1 if NaN); 2-D y, x give (N, channels, dim, dim).
     The polarised jets serve d_in <= 2; other inputs (and unfused graphs) take the reference's
-    route.  The identity part of f(x) + x has zero Hessian."""
+    route.  A network with hessian_jet=True is served by one second-order jet for d_in = 2 and 3
+    (counted in HESS_JETS).  The identity part of f(x) + x has zero Hessian."""
     try:
         with _lower.immediate():  # the polarised jets' values are read in this call
             H = _hessian_core(y, x, "hessian")

@@ -42,10 +42,13 @@ def get_network(cfg, in_features, out_features):
     """base/networks.py:12-17: cfg.network 'siren' -> MLP(..., nonlinearity=cfg.nonlinearity) (a relu /
     elu one, or a width above 256, is the reference's plain torch network: TorchMLP).
     cfg.insr_precision (optional, default None = the library default, fp32-accurate split-bf16)
-    selects the matrix-core precision of the net's jets: 'fp32', 'bf16x6', 'bf16x3' or 'bf16'."""
+    selects the matrix-core precision of the net's jets: 'fp32', 'bf16x6', 'bf16x3' or 'bf16'.
+    cfg.insr_hessian_jet (optional, default False): hessian() / laplace(normalize=True) of this network
+    run the second-order jet (MLP.hessian_jet)."""
     if cfg.network == 'siren':
         return MLP(in_features, out_features, cfg.num_hidden_layers, cfg.hidden_features,
-                   nonlinearity=cfg.nonlinearity, precision=getattr(cfg, "insr_precision", None))
+                   nonlinearity=cfg.nonlinearity, precision=getattr(cfg, "insr_precision", None),
+                   hessian_jet=bool(getattr(cfg, "insr_hessian_jet", False)))
     raise NotImplementedError(cfg.network)
 
 
@@ -175,7 +178,7 @@ class _MLPArgs:
     """MLP's constructor arguments by name (the signature of MLP.__init__), for __new__'s dispatch."""
 
     def __init__(self, in_features, out_features, num_hidden_layers, hidden_features,
-                 outermost_linear=True, nonlinearity='relu', weight_init=None, precision=None):
+                 outermost_linear=True, nonlinearity='relu', weight_init=None, precision=None, hessian_jet=False):
         self.in_features, self.out_features = in_features, out_features
         self.num_hidden_layers, self.hidden_features = num_hidden_layers, hidden_features
         self.outermost_linear, self.nonlinearity, self.weight_init = outermost_linear, nonlinearity, weight_init
@@ -196,12 +199,15 @@ class MLP(nn.Module):
         return super().__new__(cls)
 
     def __init__(self, in_features, out_features, num_hidden_layers, hidden_features,
-                 outermost_linear=True, nonlinearity='relu', weight_init=None, precision=None):
+                 outermost_linear=True, nonlinearity='relu', weight_init=None, precision=None, hessian_jet=False):
         super().__init__()
         self.in_features, self.out_features = in_features, out_features
         self.num_hidden_layers, self.hidden_features = num_hidden_layers, hidden_features
         self.kernel_width = kernel_width(hidden_features)
         self.set_precision(precision)
+        # opt-in: hessian() / laplace(normalize=True) of d_in = 2 / 3 inputs from ONE second-order jet
+        # (base/_hess.py) instead of the polarised Laplacian jets (d_in = 2) / the autograd route (d_in = 3)
+        self.hessian_jet = bool(hessian_jet)
         layers = [nn.Linear(in_features, hidden_features), Sine()]
         for _ in range(num_hidden_layers):
             layers += [nn.Linear(hidden_features, hidden_features), Sine()]

@@ -48,8 +48,69 @@ def time_it(fn, reps):
     return e0.elapsed_time(e1) / reps * 1e3  # us
 
 
+HESS_SHAPES = [((2, 1, 4, 128), 16708), ((3, 3, 4, 128), 16384)]  # (d_in, d_out, L, W), points
+
+
+def hessian_lines(args):
+    """--hessian: the second-order jet (csrc/jet_hess.hpp) against what hessian() does without it (the
+    polarised Laplacian jets for d_in = 2, the reference-semantics autograd route for d_in = 3), through
+    base.hessian: the forward, and forward + backward of sum(H . R) into .grad including the sums.  The two
+    routes alternate line by line, `rounds` times; a last line per shape times the two kernels alone
+    (forward; backward + partial-row sums into the flat gradient)."""
+    import base
+    from base import _native as nat
+    lib = nat.load()
+    for (din, dout, L, W), n in HESS_SHAPES:
+        torch.manual_seed(0)
+        net = base.MLP(din, dout, L, W, nonlinearity="sine").cuda()
+        flat, P = net.flat_params(), net.param_count
+        x = (torch.rand(n, din, device="cuda") * 2 - 1).contiguous()
+        R = torch.randn(n, dout, din, din, device="cuda")
+
+        def api_fwd(flag):
+            net.hessian_jet = flag
+            xg = x.detach().requires_grad_(True)
+            return base.hessian(net(xg), xg)[0]
+
+        def api_fwd_bwd(flag):
+            net.zero_grad(set_to_none=True)
+            (api_fwd(flag) * R).sum().backward()
+
+        for r in range(args.rounds):
+            for flag in (True, False):
+                rec = {"shape": [din, dout, L, W], "n": n, "route": "jet" if flag else "present", "round": r,
+                       "fwd_us": round(time_it(lambda: api_fwd(flag), args.reps), 1),
+                       "fwd_bwd_us": round(time_it(lambda: api_fwd_bwd(flag), args.reps), 1)}
+                print(json.dumps(rec), flush=True)
+        y = torch.empty(n, dout, device="cuda")
+        dy = torch.empty(n, dout, din, device="cuda")
+        h = torch.empty(n, dout, din, din, device="cuda")
+        gy, gdy, gh = torch.randn_like(y), torch.randn_like(dy), torch.randn_like(h)
+        act = torch.empty(lib.insr_hess_act_bytes(n, din, L, W) // 4, device="cuda")
+        nb, stride = lib.insr_hess_partial_blocks(n, din, W), lib.insr_jet_partial_stride(din, dout, L, W)
+        part = torch.empty(nb * stride, device="cuda")
+        g = torch.zeros(P, device="cuda")
+        st = nat.stream_of(x.device)
+
+        def fwd():
+            nat.check(lib.insr_siren_hess_fwd(nat.ptr(x), n, din, dout, L, W, nat.ptr(flat), nat.ptr(y), nat.ptr(dy),
+                                              nat.ptr(h), nat.ptr(act), st), "hess_fwd")
+
+        def bwdg():
+            nat.check(lib.insr_siren_hess_bwd(nat.ptr(x), n, din, dout, L, W, nat.ptr(flat), nat.ptr(act),
+                                              nat.ptr(gy), nat.ptr(gdy), nat.ptr(gh), nat.ptr(part), st), "hess_bwd")
+            nat.check(lib.insr_reduce_partials_strided(nat.ptr(part), nb, P, stride, nat.ptr(g), 0, st), "reduce")
+
+        tf = time_it(fwd, args.reps)
+        fwd()
+        print(json.dumps({"shape": [din, dout, L, W], "n": n, "route": "jet kernels", "nb": nb,
+                          "fwd_us": round(tf, 2), "bwd_grad_us": round(time_it(bwdg, args.reps), 2)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--hessian", action="store_true", help="the Hessian lines (see hessian_lines) instead of the jets")
+    ap.add_argument("--rounds", type=int, default=3, help="--hessian: alternations of the two routes")
     ap.add_argument("--nets", default="fluid_pres,fluid_vel")
     ap.add_argument("--sizes", default="324,2048,8192,16384,65536")
     ap.add_argument("--modes", default="value,grad,lap")
@@ -60,6 +121,8 @@ def main():
     ap.add_argument("--bwd-f16", type=int, default=-1, help="INSR_JET_BWD_F16 mask (-1: library default)")
     ap.add_argument("--lib", default=None, help="alternative build of libinsr_hip.so (flag studies)")
     args = ap.parse_args()
+    if args.hessian:
+        return hessian_lines(args)
     import base
     from base import _native as nat
     lib = nat.load(args.lib, check_build=args.lib is None)
