@@ -205,7 +205,7 @@ int insr_siren_jet_fwd_multi(const InsrJetJob* jobs, int n_jobs, int d_in, int d
  *            (insr_jet_partial_blocks(n, d_in, width, mode) rows of
  *            insr_jet_partial_stride(...) floats; the first param_count are used).
  * Sum the rows with insr_reduce_partials_strided into the network's flat .grad.
- * The gradient w.r.t. x is not produced (the reference never reads it).
+ * The gradient w.r.t. x comes from insr_siren_jet_bwd_x (below), on request.
  * Replaces: the autograd backward of loss.backward() (base/baseModel.py:77).
  */
 int insr_siren_jet_bwd(const float* x, long n_points, int d_in, int d_out, int num_hidden,
@@ -754,6 +754,34 @@ int insr_siren_hess_fwd(const float* x, long n_points, int d_in, int d_out, int 
 int insr_siren_hess_bwd(const float* x, long n_points, int d_in, int d_out, int num_hidden, int width,
                         const float* params, const float* act, const float* gy, const float* gdy,
                         const float* ghess, float* partial, void* stream);
+
+/*
+ * The adjoint of the sample coordinates of a reverse jet (csrc/jet_xadj.hpp): what autograd leaves in
+ * x.grad -- and sends on through x -- when a loss of y, gradient / jacobian / divergence (dy) and laplace
+ * (lap) is differentiated.  x enters a jet through the first layer's value stream only (its tangent
+ * streams are W_0's columns, its Laplacian stream is 0), so
+ *     gx[p][k] = sum_m W_0[m][k] * (value-stream adjoint of layer 0 at point p, neuron m)
+ * after the reverse sweep over all the jet's streams: one launch, one 16-point tile per block, no weight
+ * gradients, no partial rows, no sums.  It reads the streams the forward saved (`act`, the layout of
+ * insr_jet_act_bytes) and is independent of the parameter backward of the same call.
+ *   mode  the forward's full call mode: its jet-mode bits select the streams; the arithmetic is exact
+ *         fp32 whatever its precision and knob bits say.
+ *   gy (n, d_out), gdy (n, d_out, d_in) [GRAD, LAP], glap (n, d_out) [LAP]: adjoints, any may be NULL
+ *         (= zero); all NULL zero-fills gx.
+ *   gx   (n, d_in), overwritten: rows 0 .. n - 1, nothing past them.
+ * insr_siren_jet_bwd_x_supported: 1 where a kernel is compiled (d_in 1..3, d_out 1..3, widths 32 / 64 /
+ * 128 / 256) AND the forward of a call with this mode leaves saved streams (the recompute backward,
+ * insr_jet_bwd_path() == 3, saves none); host only, callers take their own route where it answers 0.
+ * Asynchronous on `stream`, no state, no allocation (capturable).  n == 0 returns 0 without a launch; a
+ * bad shape or mode, n > 2^31 - 16 or a NULL params / act / gx returns INSR_EINVAL (a width outside the
+ * compiled set: INSR_EWIDTH) before anything touches the device.
+ * Replaces: the x half of loss.backward() through MLP.forward and the diff ops (base/networks.py:67-71,
+ * base/diff_ops.py:33-82), which plain autograd produces whenever x requires grad.
+ */
+int insr_siren_jet_bwd_x_supported(int d_in, int d_out, int num_hidden, int width, int mode);
+int insr_siren_jet_bwd_x(long n_points, int d_in, int d_out, int num_hidden, int width, int mode,
+                         const float* params, const float* act, const float* gy, const float* gdy,
+                         const float* glap, float* gx, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,9 @@
     from base import BaseModel, gradient, divergence, laplace, jacobian, \
         sample_random, sample_uniform, sample_boundary, sample_boundary2D_separate, get_network
 
-The hot path runs on libinsr_hip.so (gfx950); see DESIGN.md.
+The hot path runs on libinsr_hip.so (gfx950); see DESIGN.md.  Gradients with respect to the sample
+coordinates (x.grad, and what flows on through x) are opt-in per network: MLP(..., coord_grad=True),
+net.coord_grad = True or cfg.insr_coord_grad (base/networks.py).
 """
 from .baseModel import BaseModel
 from .diff_ops import *  # noqa: F401,F403

@@ -9,7 +9,8 @@ The node sits beside _jet._SirenJet: its reverse jet writes the network's flat .
 partial-row hand-over (PendingSums "rows"), so grad_for_backward, grad_write_begin / end and
 defer_reductions behave as for a fused-path reverse jet; it launches at once (it does not join a
 batched_backward queue).  Under create_graph=True it differentiates itself with torch ops
-(torch_hess_jet), as _SirenJet does.  Exact fp32 whatever the network's precision.
+(torch_hess_jet), as _SirenJet does.  Exact fp32 whatever the network's precision.  With MLP.coord_grad a
+plain backward also returns the adjoint of x, through torch ops on torch_hess_jet (third order: no kernel).
 """
 import ctypes
 
@@ -97,13 +98,22 @@ class _SirenHess(torch.autograd.Function):
         none = (None,) * (3 + len(mlp.plist()))
         if torch.is_grad_enabled():  # create_graph=True: reference semantics, to any order
             return _reference_backward(ctx, (gy, gdy, gh))
-        if not ctx.save or not any(p.requires_grad for p in mlp.plist()):
-            return none
         if gy is None and gdy is None and gh is None:
             return none
+        res = none
+        if getattr(mlp, "coord_grad", False) and ctx.needs_input_grad[0]:
+            # the adjoint of x, on request (MLP.coord_grad): a third-order quantity, through torch ops (no
+            # kernel is compiled for it)
+            from . import losses
+            losses.materialize_for(gy, gdy, gh)
+            key = ("hess", ctx.x2.shape[1], mlp.out_features, mlp.num_hidden_layers, mlp.kernel_width)
+            gx = _jet._torch_x_adjoint(mlp, lambda xd: torch_hess_jet(mlp, xd), ctx.x2, (gy, gdy, gh), key)
+            res = (gx,) + none[1:]
+        if not ctx.save or not any(p.requires_grad for p in mlp.plist()):
+            return res
         c = lambda t: None if t is None else (t if t.is_contiguous() else t.contiguous())  # noqa: E731
         _launch_bwd(mlp, ctx.x2, ctx.act, c(gy), c(gdy), c(gh))
-        return none
+        return res
 
 
 def _reference_backward(ctx, grads):
@@ -175,7 +185,7 @@ def run_hess_jet(mlp, x):
     if _jet._Fused.pending is not None:
         raise _jet.UnsupportedPattern("a second-order jet inside a fused_forwards scope (it launches at once)")
     x2, lead = _jet._flatten_x(x, din)
-    y, dy, hess = _SirenHess.apply(x2, mlp, _jet._needs_save(mlp), *mlp.plist())
+    y, dy, hess = _SirenHess.apply(x2, mlp, _jet._needs_save(mlp, x2), *mlp.plist())
     if x.dim() == 2:
         return y, dy, hess
     return y.view(*lead, dout), dy.view(*lead, dout, din), hess.view(*lead, dout, din, din)

@@ -48,8 +48,15 @@ def _flatten_x(x, din):
     return x2.contiguous(), lead
 
 
-def _needs_save(mlp):
-    return torch.is_grad_enabled() and any(p.requires_grad for p in mlp.plist())
+def _needs_save(mlp, x2=None):
+    """Does the forward of this call save its streams: a parameter requires grad, or the network returns
+    coordinate gradients (MLP.coord_grad) and the call's points x2 require grad -- a frozen network saves
+    too then (the x-adjoint launch reads the streams, _x_adjoint)."""
+    if not torch.is_grad_enabled():
+        return False
+    if any(p.requires_grad for p in mlp.plist()):
+        return True
+    return bool(getattr(mlp, "coord_grad", False)) and x2 is not None and x2.requires_grad
 
 
 # Optional per-launch HIP-event timing (bench.py's roofline leg).  When enabled,
@@ -128,22 +135,28 @@ class _SirenJet(torch.autograd.Function):
             # create_graph=True: the caller differentiates THROUGH this jet (a diff op on a graph the
             # jet matcher does not recognise, base/diff_ops.py fallback): reference semantics
             return _reference_backward(ctx, grads)
-        if not ctx.save or not any(p.requires_grad for p in mlp.plist()):
-            return none
         gy = grads[0]
         gdy = grads[1] if mode != nat.MODE_VALUE else None
         glap = grads[2] if mode == nat.MODE_LAP else None
         if gy is None and gdy is None and glap is None:
             return none
         c = lambda t: None if t is None else (t if t.is_contiguous() else t.contiguous())  # noqa: E731
-        job = _BwdJob(mlp, mode, ctx.cmode, ctx.x2, ctx.act, c(gy), c(gdy), c(glap))
+        gy, gdy, glap = c(gy), c(gdy), c(glap)
+        res = none
+        if getattr(mlp, "coord_grad", False) and ctx.needs_input_grad[0]:
+            # the adjoint of x, on request (MLP.coord_grad): its own launch, now, on autograd's stream --
+            # whether or not a parameter requires grad, and independent of the parameter job below
+            res = (_x_adjoint(mlp, mode, ctx.cmode, ctx.x2, ctx.act, gy, gdy, glap),) + none[1:]
+        if not ctx.save or not any(p.requires_grad for p in mlp.plist()):
+            return res
+        job = _BwdJob(mlp, mode, ctx.cmode, ctx.x2, ctx.act, gy, gdy, glap)
         job.outs = ctx.out_bufs
         queue = _BwdBatch.queue_for(job)
         if queue is not None:  # launched with the network's other jobs at the scope's exit
             queue.append(job)
         else:
             _launch_bwd(job)
-        return none
+        return res
 
 
 def torch_jet(mlp, x2, mode):
@@ -214,7 +227,59 @@ def _reference_backward(ctx, grads):
     return tuple(res)
 
 
-REF_STATS = {"backward": 0}  # reference-semantics (create_graph) backwards run through _SirenJet
+# reference-semantics backwards run through the jet nodes: create_graph passes ("backward"), and x-adjoints
+# of a plain backward that no kernel served ("x_backward": _torch_x_adjoint)
+REF_STATS = {"backward": 0, "x_backward": 0}
+
+
+def _x_adjoint(mlp, mode, cmode, x2, act, gy, gdy, glap):
+    """The adjoint of the coordinates x2 of one jet call for the (contiguous) adjoints gy / gdy / glap of
+    its outputs: ONE launch of insr_siren_jet_bwd_x on the forward's saved streams, at once, on autograd's
+    current stream (it joins no batched_backward queue and holds back no sums).  Where no kernel serves the
+    call (insr_siren_jet_bwd_x_supported) or the forward saved nothing (the recompute policy): torch ops
+    with the reference's semantics (_torch_x_adjoint)."""
+    from . import losses
+    n, din = x2.shape
+    L, W, dout = mlp.num_hidden_layers, mlp.kernel_width, mlp.out_features
+    lib = nat.lib()
+    cur = torch.cuda.current_stream(x2.device)
+    for t in (gy, gdy, glap):  # lazy loss groups among the adjoints: read as data here
+        g = losses.lazy_group_of(t)
+        if g is not None:
+            g.materialize(cur)
+    if act is None or not lib.insr_siren_jet_bwd_x_supported(din, dout, L, W, cmode):
+        return _torch_x_adjoint(mlp, lambda xd: torch_jet(mlp, xd, mode), x2, (gy, gdy, glap),
+                                (MODE_NAMES[mode], din, dout, L, W))
+    gx = torch.empty(n, din, device=x2.device, dtype=torch.float32)
+    with _timed("bwdx", mode, n, W, (din, dout, L)):
+        rc = lib.insr_siren_jet_bwd_x(n, din, dout, L, W, cmode, nat.ptr(mlp.flat_params()), nat.ptr(act),
+                                      nat.ptr(gy), nat.ptr(gdy), nat.ptr(glap), nat.ptr(gx),
+                                      ctypes.c_void_p(cur.cuda_stream))
+    nat.check(rc, "insr_siren_jet_bwd_x")
+    return gx
+
+
+_X_WARNED = set()
+
+
+def _torch_x_adjoint(mlp, jet, x2, grads, key):
+    """The x-adjoint of a jet call through torch ops: jet(xd) -- torch_jet / torch_hess_jet of the network --
+    on a detached copy of x2 that requires grad, then autograd.grad with the adjoints as grad_outputs.  x
+    only (the parameters keep their own route), first order (not differentiable further).  Off the hot
+    path: counted in REF_STATS["x_backward"], one warning per shape."""
+    if key not in _X_WARNED:
+        _X_WARNED.add(key)
+        import warnings
+        warnings.warn(f"coordinate gradient of a {key[0]} jet of SIREN(in={key[1]}, out={key[2]}, hidden layers="
+                      f"{key[3]}, width={key[4]}): no kernel serves this call (or its forward saved no streams); "
+                      "running torch ops", stacklevel=2)
+    with torch.enable_grad():
+        xd = x2.detach().requires_grad_(True)
+        outs = jet(xd)
+        prs = [(o, g) for o, g in zip(outs, grads) if o is not None and g is not None]
+        (gx,) = torch.autograd.grad([o for o, _ in prs], [xd], grad_outputs=[g.detach() for _, g in prs])
+    REF_STATS["x_backward"] += 1
+    return gx
 
 
 class _BwdJob:
@@ -762,7 +827,7 @@ def run_jet(mlp, x, mode):
             f"in {MODE_NAMES[mode]} mode")
     x2, lead = _flatten_x(x, din)
     params = tuple(mlp.plist())
-    outs = _SirenJet.apply(x2, mode, mlp, _needs_save(mlp), *params)
+    outs = _SirenJet.apply(x2, mode, mlp, _needs_save(mlp, x2), *params)
     if x.dim() == 2:  # no view node: keeps y.grad_fn == our node (identity-stable, see match())
         y = outs[0]
         dy = outs[1] if mode != nat.MODE_VALUE else None

@@ -209,6 +209,8 @@ SIGNATURES = {
     "insr_hess_partial_bytes": (_L, [_L, _I, _I, _I, _I]),
     "insr_siren_hess_fwd": (_I, [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "insr_siren_hess_bwd": (_I, [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "insr_siren_jet_bwd_x_supported": (_I, [_I, _I, _I, _I, _I]),
+    "insr_siren_jet_bwd_x": (_I, [_L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 

@@ -44,11 +44,14 @@ def get_network(cfg, in_features, out_features):
     cfg.insr_precision (optional, default None = the library default, fp32-accurate split-bf16)
     selects the matrix-core precision of the net's jets: 'fp32', 'bf16x6', 'bf16x3' or 'bf16'.
     cfg.insr_hessian_jet (optional, default False): hessian() / laplace(normalize=True) of this network
-    run the second-order jet (MLP.hessian_jet)."""
+    run the second-order jet (MLP.hessian_jet).
+    cfg.insr_coord_grad (optional, default False): loss.backward() also returns the gradient with respect
+    to the coordinates of this network's calls (MLP.coord_grad)."""
     if cfg.network == 'siren':
         return MLP(in_features, out_features, cfg.num_hidden_layers, cfg.hidden_features,
                    nonlinearity=cfg.nonlinearity, precision=getattr(cfg, "insr_precision", None),
-                   hessian_jet=bool(getattr(cfg, "insr_hessian_jet", False)))
+                   hessian_jet=bool(getattr(cfg, "insr_hessian_jet", False)),
+                   coord_grad=bool(getattr(cfg, "insr_coord_grad", False)))
     raise NotImplementedError(cfg.network)
 
 
@@ -178,7 +181,8 @@ class _MLPArgs:
     """MLP's constructor arguments by name (the signature of MLP.__init__), for __new__'s dispatch."""
 
     def __init__(self, in_features, out_features, num_hidden_layers, hidden_features,
-                 outermost_linear=True, nonlinearity='relu', weight_init=None, precision=None, hessian_jet=False):
+                 outermost_linear=True, nonlinearity='relu', weight_init=None, precision=None, hessian_jet=False,
+                 coord_grad=False):
         self.in_features, self.out_features = in_features, out_features
         self.num_hidden_layers, self.hidden_features = num_hidden_layers, hidden_features
         self.outermost_linear, self.nonlinearity, self.weight_init = outermost_linear, nonlinearity, weight_init
@@ -199,7 +203,8 @@ class MLP(nn.Module):
         return super().__new__(cls)
 
     def __init__(self, in_features, out_features, num_hidden_layers, hidden_features,
-                 outermost_linear=True, nonlinearity='relu', weight_init=None, precision=None, hessian_jet=False):
+                 outermost_linear=True, nonlinearity='relu', weight_init=None, precision=None, hessian_jet=False,
+                 coord_grad=False):
         super().__init__()
         self.in_features, self.out_features = in_features, out_features
         self.num_hidden_layers, self.hidden_features = num_hidden_layers, hidden_features
@@ -208,6 +213,12 @@ class MLP(nn.Module):
         # opt-in: hessian() / laplace(normalize=True) of d_in = 2 / 3 inputs from ONE second-order jet
         # (base/_hess.py) instead of the polarised Laplacian jets (d_in = 2) / the autograd route (d_in = 3)
         self.hessian_jet = bool(hessian_jet)
+        # opt-in: a plain loss.backward() returns the adjoint of the coordinates x of this network's calls
+        # (x.grad, and every gradient that flows on through x) -- one more launch per reverse jet
+        # (base/_jet.py _x_adjoint, csrc/jet_xadj.hpp).  Off: the reverse jets return None for x, as the
+        # training loops of the INSR-PDE models want (their diff ops make x require grad in every call,
+        # and nothing reads x.grad).  create_graph=True passes return it either way.
+        self.coord_grad = bool(coord_grad)
         layers = [nn.Linear(in_features, hidden_features), Sine()]
         for _ in range(num_hidden_layers):
             layers += [nn.Linear(hidden_features, hidden_features), Sine()]

@@ -2,6 +2,7 @@
 (HIP events around R launches, no host gaps), for both kernel variants.
 
     python tools/kbench.py [--nets fluid_pres,fluid_vel] [--sizes 324,4096,16384]
+    python tools/kbench.py --hessian | --xgrad
 """
 import argparse
 import json
@@ -107,10 +108,82 @@ def hessian_lines(args):
                           "fwd_us": round(tf, 2), "bwd_grad_us": round(time_it(bwdg, args.reps), 2)}), flush=True)
 
 
+XGRAD_SHAPES = [((2, 1, 4, 128), "lap", 16708), ((2, 2, 4, 128), "value", 16708)]  # shape, jet mode, points
+
+
+def xgrad_lines(args):
+    """--xgrad: what the coordinate gradient (MLP.coord_grad, csrc/jet_xadj.hpp) adds to a backward.  Per
+    shape, `rounds` times, alternating: the backward of one jet call through autograd (the adjoints handed to
+    torch.autograd.backward, so no loss arithmetic is timed) with the flag off, with the flag on (+ the
+    x-adjoint launch), and with the flag off followed by the torch route the nodes take where no kernel serves
+    a call (_jet._torch_x_adjoint); a last line per shape times the two kernels alone: the parameter backward
+    into .grad including its sums, and insr_siren_jet_bwd_x."""
+    import warnings
+    import base
+    from base import _jet, _native as nat
+    lib = nat.load()
+    for (din, dout, L, W), mname, n in XGRAD_SHAPES:
+        mode = MODES[mname]
+        torch.manual_seed(0)
+        net = base.MLP(din, dout, L, W, nonlinearity="sine", coord_grad=True).cuda()
+        x = (torch.rand(n, din, device="cuda") * 2 - 1).contiguous()
+        xg = x.detach().requires_grad_(True)
+        outs = [o for o in _jet.run_jet(net, xg, mode) if o is not None]
+        adj = [torch.randn_like(o) for o in outs]
+        full = (adj + [None, None])[:3]
+
+        def bwd(flag):
+            net.coord_grad = flag
+            xg.grad = None
+            torch.autograd.backward(outs, adj, retain_graph=True)
+
+        def bwd_torch():
+            bwd(False)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                _jet._torch_x_adjoint(net, lambda xd: _jet.torch_jet(net, xd, mode), xg, full, (mname, din, dout, L, W))
+
+        for r in range(args.rounds):
+            rec = {"shape": [din, dout, L, W], "mode": mname, "n": n, "round": r,
+                   "bwd_flag_off_us": round(time_it(lambda: bwd(False), args.reps), 1),
+                   "bwd_flag_on_us": round(time_it(lambda: bwd(True), args.reps), 1),
+                   "bwd_torch_route_us": round(time_it(bwd_torch, args.reps), 1)}
+            print(json.dumps(rec), flush=True)
+        net.ensure_wsplit()
+        cmode = net.call_mode(mode)
+        flat, P = net.flat_params(), net.param_count
+        y = torch.empty(n, dout, device="cuda")
+        dy = torch.empty(n, dout, din, device="cuda")
+        lap = torch.empty(n, dout, device="cuda")
+        act = torch.empty(lib.insr_jet_act_bytes(n, din, L, W, cmode) // 4, device="cuda")
+        st = nat.stream_of(x.device)
+        nat.check(lib.insr_siren_jet_fwd(nat.ptr(x), n, din, dout, L, W, cmode, nat.ptr(flat), nat.ptr(y), nat.ptr(dy),
+                                         nat.ptr(lap), nat.ptr(act), st), "fwd")
+        work = torch.empty(max(lib.insr_jet_bwd_work_bytes(n, din, dout, L, W, cmode) // 4, 1), device="cuda")
+        g = torch.zeros(P, device="cuda")
+        gx = torch.empty(n, din, device="cuda")
+        gy, gdy, glap = full
+
+        def bwdg():
+            nat.check(lib.insr_siren_jet_bwd_grad(nat.ptr(x), n, din, dout, L, W, cmode, nat.ptr(flat), nat.ptr(act),
+                                                  nat.ptr(gy), nat.ptr(gdy), nat.ptr(glap), nat.ptr(work), nat.ptr(g),
+                                                  0, st), "bwd_grad")
+
+        def bwdx():
+            nat.check(lib.insr_siren_jet_bwd_x(n, din, dout, L, W, cmode, nat.ptr(flat), nat.ptr(act), nat.ptr(gy),
+                                               nat.ptr(gdy), nat.ptr(glap), nat.ptr(gx), st), "bwd_x")
+
+        print(json.dumps({"shape": [din, dout, L, W], "mode": mname, "n": n, "route": "kernels",
+                          "path": lib.insr_jet_bwd_path(n, din, dout, L, W, cmode),
+                          "bwd_grad_us": round(time_it(bwdg, args.reps), 2),
+                          "bwd_x_us": round(time_it(bwdx, args.reps), 2)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--xgrad", action="store_true", help="the coordinate-gradient lines (see xgrad_lines)")
     ap.add_argument("--hessian", action="store_true", help="the Hessian lines (see hessian_lines) instead of the jets")
-    ap.add_argument("--rounds", type=int, default=3, help="--hessian: alternations of the two routes")
+    ap.add_argument("--rounds", type=int, default=3, help="--hessian / --xgrad: alternations of the routes")
     ap.add_argument("--nets", default="fluid_pres,fluid_vel")
     ap.add_argument("--sizes", default="324,2048,8192,16384,65536")
     ap.add_argument("--modes", default="value,grad,lap")
@@ -123,6 +196,8 @@ def main():
     args = ap.parse_args()
     if args.hessian:
         return hessian_lines(args)
+    if args.xgrad:
+        return xgrad_lines(args)
     import base
     from base import _native as nat
     lib = nat.load(args.lib, check_build=args.lib is None)
