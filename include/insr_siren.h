@@ -695,6 +695,39 @@ int insr_sample_boxes_rep(const InsrBox* boxes, int n_boxes, int dim, int reps, 
                           unsigned long long seed, void* state, void* stream);
 
 /*
+ * Mesh points of one phase iteration in ONE launch (csrc/mesh_sampler.hip): n points uniform in the
+ * volume of a tet mesh (nc = 4, dim = 3) or over the area of a triangle mesh (nc = 3, dim = 2 or 3),
+ * the element chosen with probability proportional to its measure.  Per point, from m =
+ * insr_mesh_uniforms_per_point(nc) uniforms in [0, 1) of 24-bit resolution (6 for tets, 4 for
+ * triangles):
+ *   u = u0 + u1 2^-24 in fp64, elem = min(#{i : cdf[i] <= u}, k - 1);
+ *   tets: e_i = -log(max(r_i, 1e-30)), bary = e / sum e; triangles: su = sqrt(r0),
+ *   bary = (1 - su, su (1 - r1), su r1); out = sum_i bary_i corner_i in fp32.
+ * insr_mesh_points takes the caller's uniforms ((n, m) row-major).  insr_sample_mesh draws them from
+ * the stream of insr_sample_boxes, with the same `state` object (insr_sampler_state_bytes): value
+ * v = p m + j of the launch is Philox4x32-10(seed, state[0] + v / 4)[v % 4] mapped as (bits >> 8) 2^-24,
+ * and the launch advances state[0] by ceil(n m / 4) itself -- exactly the numbers an insr_sample_boxes
+ * launch of n m values in [0, 1) consumes, so a captured graph draws fresh points on every replay and a
+ * following box draw continues the stream where it would have.  `elem` ((n) element indices) may be
+ * NULL.  n = 0 returns 0 without a launch; a NULL mesh / cdf / corners / out / uniforms / state, nc
+ * outside {3, 4}, dim outside {2, 3}, tets in 2-d, k < 1 or beyond 2^31 - 1, n < 0 or beyond the grid
+ * bound return INSR_EINVAL before any launch.
+ * Replaces: sample_volume / sample_surface (elasticity/torchgp/sample_volume.py, sample_surface.py;
+ * elasticity/sampling.py:4-9) as called at elasticity/model.py:200-207.
+ */
+typedef struct InsrMesh {
+  const double* cdf;     /* (k) normalised cumulative measure, cdf[k-1] == 1 */
+  const float* corners;  /* (k, nc, dim) row-major vertex coordinates per element */
+  long k;                /* elements */
+  int nc;                /* corners per element: 4 tets (dim 3), 3 triangles (dim 2 or 3) */
+  int dim;
+} InsrMesh;
+long insr_mesh_uniforms_per_point(int nc);
+int insr_mesh_points(const InsrMesh* mesh, const float* uniforms, long n, float* out, int* elem, void* stream);
+int insr_sample_mesh(const InsrMesh* mesh, long n, float* out, int* elem, unsigned long long seed, void* state,
+                     void* stream);
+
+/*
  * One advection iteration's forward, residual and reverse in ONE launch (round 6; csrc/advect_iter.hip):
  * the reference's Advection1DModel._advect (advection/model.py:68-91) on a 1 -> 1 SIREN of width 64 and
  * num_hidden (1..3) hidden layers -- the draw of n interior points in [box_lo[0], box_hi[0]) and

@@ -193,6 +193,9 @@ SIGNATURES = {
     "insr_sampler_state_bytes": (_L, []),
     "insr_sample_boxes": (_I, [_P, _I, _I, ctypes.c_ulonglong, _P, _P]),
     "insr_sample_boxes_rep": (_I, [_P, _I, _I, _I, _P, ctypes.c_ulonglong, _P, _P]),
+    "insr_mesh_uniforms_per_point": (_L, [_I]),
+    "insr_mesh_points": (_I, [_P, _P, _L, _P, _P, _P]),
+    "insr_sample_mesh": (_I, [_P, _L, _P, _P, ctypes.c_ulonglong, _P, _P]),
     "insr_advect1d_rows": (_L, [_L]),
     "insr_advect1d_iteration": (_I, [_P, _P, _I, _I, _L, _L, _P, _P, _F, _F, _F, _F, ctypes.c_ulonglong, _P, _P,
                                      _P, _L, _P, _P, _P]),
@@ -264,6 +267,11 @@ MAX_BOXES = 8  # INSR_MAX_BOXES
 class Box(ctypes.Structure):
     """struct InsrBox (include/insr_siren.h): one box of insr_sample_boxes."""
     _fields_ = [("out", _P), ("n", _L), ("lo", _F * 3), ("hi", _F * 3)]
+
+
+class Mesh(ctypes.Structure):
+    """struct InsrMesh (include/insr_siren.h): the element table of insr_mesh_points / insr_sample_mesh."""
+    _fields_ = [("cdf", _P), ("corners", _P), ("k", _L), ("nc", _I), ("dim", _I)]
 
 
 EL_TERMS = 8  # INSR_EL_TERMS; term ids INSR_EL_ARAP ... INSR_EL_SPHERE

@@ -18,7 +18,7 @@ _AFFINE = {}  # (N, side-key, epsilon, device) -> (scale, shift) constant tensor
 
 __all__ = ["sample_uniform", "sample_random", "sample_boundary", "sample_boundary2D_separate",
            "sample_boundary2D_pair", "sample_random_and_bands2D", "sample_boxes", "sample_boxes_into",
-           "merge_samples"]
+           "sample_mesh_into", "merge_samples"]
 
 
 def sample_uniform(resolution, sdim=1, device="cpu", flatten=True):
@@ -516,4 +516,34 @@ def sample_boxes_into(buf, boxes):
         arr[k] = nat.Box(buf.data_ptr() + 4 * dim * int(row0), int(n), f3(*(list(lo) + pad)), f3(*(list(hi) + pad)))
     nat.check(nat.lib().insr_sample_boxes(arr, len(boxes), dim, seed, nat.ptr(state), nat.stream_of(buf.device)),
               "insr_sample_boxes")
+    return buf
+
+
+def sample_mesh_into(buf, row0, n, sampler, elements=None):
+    """n volume- / area-weighted points of `sampler` (pde.mesh.MeshSampler, its table on buf's device) into
+    rows [row0, row0 + n) of an existing contiguous (R, dim) fp32 device buffer, the other rows untouched: ONE
+    launch (insr_sample_mesh) on the device stream of sample_boxes -- the same state and key (_sampler: the
+    rank folded in, restarted by a torch re-seed, created before a capture), consuming the numbers a
+    sample_boxes([(n m / dim, 0, 1)]) launch would.  elements: an (n,) int32 device tensor that receives each
+    point's element, or None."""
+    from . import _native as nat
+    if not buf.is_cuda or buf.dtype != torch.float32 or not buf.is_contiguous() or buf.dim() != 2:
+        raise nat.NativeUnavailable("sample_mesh_into: a contiguous (R, dim) fp32 GPU buffer")
+    mesh = sampler.native_table()
+    row0, n = int(row0), int(n)
+    if buf.shape[1] != mesh.dim:
+        raise ValueError(f"sample_mesh_into: the buffer has {buf.shape[1]} columns, the mesh {mesh.dim} coordinates")
+    if sampler.cdf.device != buf.device:
+        raise ValueError(f"sample_mesh_into: the mesh table is on {sampler.cdf.device}, the buffer on {buf.device}")
+    if n < 0 or row0 < 0 or row0 + n > buf.shape[0]:
+        raise ValueError(f"sample_mesh_into: rows [{row0}, {row0 + n}) outside {buf.shape[0]}")
+    if elements is not None and (elements.device != buf.device or elements.dtype != torch.int32 or
+                                 not elements.is_contiguous() or elements.numel() != n):
+        raise ValueError(f"sample_mesh_into: elements must be a contiguous ({n},) int32 tensor on {buf.device}")
+    if n == 0:
+        return buf
+    state, seed = _sampler(buf.device)
+    nat.check(nat.lib().insr_sample_mesh(ctypes.byref(mesh), n, ctypes.c_void_p(buf.data_ptr() + 4 * mesh.dim * row0),
+                                         nat.ptr(elements), seed, nat.ptr(state), nat.stream_of(buf.device)),
+              "insr_sample_mesh")
     return buf

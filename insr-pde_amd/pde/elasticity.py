@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from base import BaseModel, elastic_energy, fused_forwards, merge_samples, sample_random, sample_uniform
-from base.sampling import sample_boxes_into
+from base.sampling import sample_boxes_into, sample_mesh_into
 from base.diff_ops import jacobian_only
 
 
@@ -86,6 +86,7 @@ class ElasticityModel(BaseModel):
     # run (bench.py --shard-of K measures exactly this code).  Ranks draw independent points: the device
     # samplers fold the rank into their key (base.sampling.sampler_seed); a sharded rank's mesh draw takes
     # its uniforms from the same device stream (_mesh_draw; on the CPU a generator keyed alike).
+    # cfg.insr_mesh_batch (opt-in): the mesh draw as one launch into a persistent batch (_mesh_batch).
     def _shard(self):
         """(r, K): this process's share of the global batch (K = 1: the whole batch)."""
         emu = getattr(self.cfg, "insr_shard", None)
@@ -206,7 +207,9 @@ class ElasticityModel(BaseModel):
         """mean(f(x)^2) over the GLOBAL batch (elasticity/model.py:109-117): a sum over this
         rank's shard / the global element count, so the 'sum' all-reduce of _dp_sync gives
         the reference's mean at any world size."""
-        x = self._sample_in_training(self.sample_resolution_init)
+        x = self._mesh_batch(self.sample_resolution_init)
+        if x is None:
+            x = self._sample_in_training(self.sample_resolution_init)
         y = self.deformation_field(x)
         world = self._dp_world()
         if world == 1:
@@ -234,7 +237,9 @@ class ElasticityModel(BaseModel):
         if fast is not None:
             xa, x, fixed_l, fixed_r = fast
             return {'main': self.energy_of(x, fixed_l, fixed_r, xa=xa)}
-        x = self._sample_in_training(self.sample_resolution)
+        x = self._mesh_batch(self.sample_resolution)
+        if x is None:
+            x = self._sample_in_training(self.sample_resolution)
         fixed_l, fixed_r = self._sample_fixed_in_training(self.sample_resolution)
         return {'main': self.energy_of(x, fixed_l, fixed_r)}
 
@@ -300,6 +305,46 @@ class ElasticityModel(BaseModel):
         if boxes:
             sample_boxes_into(buf.detach(), boxes)
         return buf, x, fixed_l, fixed_r
+
+    def _mesh_batch(self, resolution):
+        """The mesh scene's iteration batch on the GPU, opt-in (cfg.insr_mesh_batch): _sample_in_training's
+        rows (the parts in sample_pattern order, this process's share of each) as ONE persistent leaf buffer
+        -- the 'uniform' rows (the mesh vertices) are written once, each 'random' part is redrawn in place by
+        ONE device launch (base.sampling.sample_mesh_into: the sample_boxes stream, capturable, fresh points
+        on every replay) instead of _mesh_draw's chain of ~12 torch launches + cat.  Same distributions,
+        the device stream (another draw than torch's generator gives); None where it does not apply.  A mesh
+        has no fixed rows."""
+        if not getattr(self.cfg, "insr_mesh_batch", False) or not self.use_mesh or \
+                torch.device(self.device).type != "cuda":
+            return None
+        if "_sample_in_training" in self.__dict__:
+            return None  # an instance-level sampler (tests pass recorded samples) takes precedence
+        d = self.dim
+        key = (resolution, self._shard())
+        cache = self.__dict__.setdefault("_insr_mesh_batch", {})
+        if key not in cache:
+            rows, draws, fill = 0, [], []
+            for s in self.sample_pattern:
+                if s == 'random':
+                    m = self._rows(resolution ** d)[1]
+                    draws.append((rows, m))
+                elif s == 'uniform':
+                    full = self.mesh_V[:, :d]
+                    a, m = self._rows(full.shape[0])
+                    fill.append((rows, full[a:a + m]))
+                else:
+                    raise NotImplementedError(s)
+                rows += m
+            buf = torch.empty(rows, d, device=self.device)
+            with torch.no_grad():
+                for r0, g in fill:
+                    buf[r0:r0 + g.shape[0]].copy_(g)
+            buf.requires_grad_(True)
+            cache[key] = (buf, [b for b in draws if b[1] > 0], self.mesh_sampler.leading(d))
+        buf, draws, sampler = cache[key]
+        for r0, m in draws:
+            sample_mesh_into(buf.detach(), r0, m, sampler)
+        return buf
 
     def energy_of(self, x, fixed_l, fixed_r, xa=None):
         """elasticity/model.py:131-189.  The interior points and the fixed points the

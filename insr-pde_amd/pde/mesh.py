@@ -17,6 +17,9 @@ without meshio / open3d:
                            Dirichlet(1,1,1,1) barycentrics (tets) / sqrt-warped barycentrics
                            (triangles), as searchsorted on a cumulative table + normalised
                            exponentials: same distributions, graph-capturable device ops.
+                           `sample_device(n)` / `points_device(uniforms)`: the same draw as ONE HIP
+                           launch (csrc/mesh_sampler.hip) on the device Philox stream of
+                           base.sample_boxes / on the caller's uniforms (GPU only).
 """
 import numpy as np
 import torch
@@ -161,6 +164,65 @@ class MeshSampler:
             su = torch.sqrt(r[:, :1])
             bary = torch.cat([1 - su, su * (1 - r[:, 1:]), su * r[:, 1:]], dim=1)
         return torch.sum(bary.unsqueeze(-1) * cor, dim=1)
+
+    # ---- the device sampler (csrc/mesh_sampler.hip): sample() in ONE launch, GPU only ----
+    def native_table(self):
+        """struct InsrMesh over self.cdf (float64) and self.corners (contiguous fp32) as they are; made once."""
+        from base import _native as nat
+        if self.cdf.device.type != "cuda":
+            raise nat.NativeUnavailable("the device mesh sampler draws on the GPU only")
+        tab = self.__dict__.get("_insr_table")
+        if tab is None or tab[1] != (self.cdf.data_ptr(), self.corners.data_ptr()):
+            if self.cdf.dtype != torch.float64 or self.corners.dtype != torch.float32 or \
+                    not self.cdf.is_contiguous() or not self.corners.is_contiguous():
+                raise ValueError("the device mesh sampler needs a contiguous float64 cdf and fp32 corners")
+            k, nc, dim = self.corners.shape
+            tab = self._insr_table = (nat.Mesh(self.cdf.data_ptr(), self.corners.data_ptr(), k, nc, dim),
+                                      (self.cdf.data_ptr(), self.corners.data_ptr()))
+        return tab[0]
+
+    def leading(self, d):
+        """The sampler of the same elements and measures whose points keep the first d coordinates
+        (sample()[:, :d]: a 2-D scene's triangles read from a 3-coordinate .obj); self when d is all of them."""
+        if d == self.corners.shape[2]:
+            return self
+        s = object.__new__(MeshSampler)
+        s.device, s.cdf, s.k = self.device, self.cdf, self.k
+        s.corners = self.corners[:, :, :d].contiguous()
+        return s
+
+    def sample_device(self, n, out=None, elements=False):
+        """sample(n) as ONE insr_sample_mesh launch on the device Philox stream of base.sample_boxes (graph-
+        capturable: the launch advances the stream itself): the (n, dim) points, written into `out` (a contiguous
+        (n, dim) fp32 tensor on the device) when given; elements=True: (points, (n,) int32 element indices)."""
+        from base.sampling import sample_mesh_into
+        self.native_table()
+        if out is None:
+            out = torch.empty(n, self.corners.shape[2], device=self.cdf.device)
+        elif tuple(out.shape) != (n, self.corners.shape[2]):
+            raise ValueError(f"out: ({n}, {self.corners.shape[2]}) expected, got {tuple(out.shape)}")
+        elem = torch.empty(n, dtype=torch.int32, device=self.cdf.device) if elements else None
+        sample_mesh_into(out, 0, n, self, elements=elem)
+        return (out, elem) if elements else out
+
+    def points_device(self, uniforms, elements=False):
+        """sample(n, uniforms=uniforms) as ONE insr_mesh_points launch: uniforms (n, uniforms_per_point()) fp32 in
+        [0, 1) on the device; elements=True: (points, (n,) int32 element indices)."""
+        from base import _native as nat
+        mesh = self.native_table()
+        m = self.uniforms_per_point()
+        if uniforms.dim() != 2 or uniforms.shape[1] != m:
+            raise ValueError(f"uniforms: (n, {m}) expected, got {tuple(uniforms.shape)}")
+        n = uniforms.shape[0]
+        if uniforms.device != self.cdf.device or uniforms.dtype != torch.float32 or not uniforms.is_contiguous():
+            raise ValueError(f"uniforms: a contiguous fp32 tensor on {self.cdf.device}")
+        out = torch.empty(n, mesh.dim, device=self.cdf.device)
+        elem = torch.empty(n, dtype=torch.int32, device=self.cdf.device) if elements else None
+        if n > 0:
+            import ctypes
+            nat.check(nat.lib().insr_mesh_points(ctypes.byref(mesh), nat.ptr(uniforms), n, nat.ptr(out), nat.ptr(elem),
+                                                 nat.stream_of(self.cdf.device)), "insr_mesh_points")
+        return (out, elem) if elements else out
 
 
 def load_mesh(path, dim, device="cpu"):

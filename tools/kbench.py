@@ -2,7 +2,7 @@
 (HIP events around R launches, no host gaps), for both kernel variants.
 
     python tools/kbench.py [--nets fluid_pres,fluid_vel] [--sizes 324,4096,16384]
-    python tools/kbench.py --hessian | --xgrad
+    python tools/kbench.py --hessian | --xgrad | --mesh
 """
 import argparse
 import json
@@ -179,8 +179,70 @@ def xgrad_lines(args):
                           "bwd_x_us": round(time_it(bwdx, args.reps), 2)}), flush=True)
 
 
+MESH_SIZES = [32768, 262144]  # the elasticity3Dbunny draw: one rank of 8, and the whole batch
+
+
+def mesh_lines(args):
+    """--mesh: one draw of n volume-weighted points in the bunny (tests/golden/bunny_mesh.npz), us per draw by
+    HIP events after warm-up, three routes alternating line by line, `rounds` times:
+      A  base.sample_boxes + MeshSampler.sample(uniforms=...)   (a sharded rank's _mesh_draw)
+      B  MeshSampler.sample(generator=None)                      (one unsharded rank's _mesh_draw)
+      C  MeshSampler.sample_device                               (insr_sample_mesh, one launch)
+    then elasticity3Dbunny as shard (0, 8) with the graph loop (bench.py --config elasticity3Dbunny --shard-of 8),
+    cfg.insr_mesh_batch off against on, ms per iteration over windows of `reps` iterations, alternating."""
+    import time
+    import base
+    from base._loop import PhaseLoop
+    from pde.config import BUNNY_FIXTURE, baseline_config
+    from pde.elasticity import ElasticityModel
+    from pde.mesh import MeshSampler, load_mesh
+    base._native.load()
+    V, E, _ = load_mesh(BUNNY_FIXTURE, 3)
+    s = MeshSampler(V.double(), E, device="cuda")
+    m = s.uniforms_per_point()
+    torch.manual_seed(0)
+    for n in MESH_SIZES:
+        out = torch.empty(n, 3, device="cuda")
+        routes = {"A boxes+sample(uniforms)": lambda: s.sample(n, uniforms=base.sample_boxes(
+                      [(n * m // 3, (0.0,) * 3, (1.0,) * 3)], 3).view(n, m)),
+                  "B sample(generator=None)": lambda: s.sample(n),
+                  "C sample_device": lambda: s.sample_device(n, out=out)}
+        for fn in routes.values():  # warm every shape the timed windows use
+            time_it(fn, 5)
+        for r in range(args.rounds):
+            for name, fn in routes.items():
+                print(json.dumps({"mesh": "bunny", "k": s.k, "n": n, "route": name, "round": r,
+                                  "us_per_draw": round(time_it(fn, args.reps), 2)}), flush=True)
+    loops = {}
+    for flag in (False, True):
+        cfg = baseline_config("elasticity3Dbunny", insr_graph=True, insr_graph_unroll=4, insr_sync_every=10 ** 9,
+                              insr_progress=False, early_stop=False, proj_dir="/tmp/insr_bench", max_n_iters=10 ** 9,
+                              insr_shard=(0, 8), insr_mesh_batch=flag)
+        torch.manual_seed(1234)
+        model = ElasticityModel(cfg)
+        model.timestep = 1
+        pl = PhaseLoop(model, ElasticityModel._solve_deformation._insr_phase, "_solve_deformation", (), {})
+        pl.start()
+        pl.run_iters(0, 2 + 4 * 3)  # eager, captured, then whole replayed groups
+        torch.cuda.synchronize()
+        loops[flag] = pl
+    i0 = 14
+    for r in range(args.rounds):
+        for flag, pl in loops.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pl.run_iters(i0, 4 * args.reps)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) / (4 * args.reps) * 1e3
+            print(json.dumps({"phase": "elasticity3Dbunny shard (0, 8)", "insr_mesh_batch": flag, "round": r,
+                              "iters": 4 * args.reps, "captured": getattr(pl.m, "_insr_capture_error", None) is None,
+                              "ms_per_iter": round(ms, 4)}), flush=True)
+        i0 += 4 * args.reps
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mesh", action="store_true", help="the mesh sampler lines (see mesh_lines)")
     ap.add_argument("--xgrad", action="store_true", help="the coordinate-gradient lines (see xgrad_lines)")
     ap.add_argument("--hessian", action="store_true", help="the Hessian lines (see hessian_lines) instead of the jets")
     ap.add_argument("--rounds", type=int, default=3, help="--hessian / --xgrad: alternations of the routes")
@@ -194,6 +256,8 @@ def main():
     ap.add_argument("--bwd-f16", type=int, default=-1, help="INSR_JET_BWD_F16 mask (-1: library default)")
     ap.add_argument("--lib", default=None, help="alternative build of libinsr_hip.so (flag studies)")
     args = ap.parse_args()
+    if args.mesh:
+        return mesh_lines(args)
     if args.hessian:
         return hessian_lines(args)
     if args.xgrad:
