@@ -588,6 +588,22 @@ int insr_svd_energy_bwd(const float* J, long n, int d, float ratio_arap, float r
                         float* gJ, void* stream);
 
 /*
+ * Hyperelastic materials on the same d x d blocks (J holds F = dq/dx itself, as above), no SVD:
+ *   out = sum_points psi(F),  gJ = gout[0] * dpsi/dF  (the first Piola stress, closed form)
+ * material 0: stable Neo-Hookean (Smith et al. 2018), shifted to psi(I) = 0, I_C = |F|_F^2, J = det F:
+ *     psi = mu/2 (I_C - d) + lam/2 (J - alpha)^2 - mu/2 log(I_C + 1) - psi_0,
+ *     alpha = 1 + (mu / lam) d / (d + 1),  psi_0 = lam/2 (1 - alpha)^2 - mu/2 log(d + 1)
+ *     (needs lam > 0, mu >= 0; finite and smooth through inversion, zero stress at F = I)
+ * material 1: St. Venant-Kirchhoff, E = (F^T F - I) / 2: psi = mu |E|_F^2 + lam/2 tr(E)^2 (mu, lam finite)
+ * Both are evaluated from G = F - I (csrc/hyperelastic.hpp), exactly 0 with zero gradient at F = I.
+ * Same reduction scheme and workspace (insr_svd_energy_work_floats()) as the SVD pair.
+ */
+int insr_hyperelastic_fwd(const float* J, long n, int d, int material, float mu, float lam, float* out,
+                          float* work, void* stream);
+int insr_hyperelastic_bwd(const float* J, long n, int d, int material, float mu, float lam, const float* gout,
+                          float* gJ, void* stream);
+
+/*
  * The elastodynamics energy of one elasticity iteration in ONE launch, with its gradient
  * for a unit seed (elasticity/model.py:131-186, elasticity/losses.py:6-20 and the 2-D case
  * of :22-39).  Replaces the jacobian + torch.svd + ~20 aten launches per direction of the
@@ -607,9 +623,14 @@ int insr_svd_energy_bwd(const float* J, long n, int d, float ratio_arap, float r
  *                   (elasticity/losses.py:22-39: in 3-D the reference's dist[:, None, None] * dir
  *                   broadcasts to (K, K, 3), a product of two sums; its gradient needs both sums,
  *                   so the launch adds a second pass over the interior rows when d = 3)
+ *   NEOHOOKEAN      sum psi(J + I), stable Neo-Hookean with (mu, lam)   (ratio: on / off; no SVD)
+ *   STVK            sum psi(J + I), St. Venant-Kirchhoff with (mu, lam) (ratio: on / off; no SVD)
+ *                   (the materials of insr_hyperelastic_fwd above; a material that is on needs J,
+ *                   NEOHOOKEAN lam > 0 and mu >= 0, STVK both finite -- else INSR_EINVAL)
  * *out = the terms of order[0 .. n_order) added in that order (cfg.energy); terms[t] = term t
  * (terms may be NULL).  gf (rows, d) / gJ (rows, d, d) (either may be NULL): d out[0] / d f, d out[0] / dJ,
- * zeros on rows no term reads.  Each term's sum is reduced in a fixed order; work:
+ * zeros on rows no term reads (gJ is written when ARAP, VOLUME, NEOHOOKEAN or STVK is on, and is left
+ * untouched otherwise).  Each term's sum is reduced in a fixed order; work:
  * insr_elastic_work_floats() floats, zero-initialised once (the launch leaves its ticket zero).
  */
 #define INSR_EL_ARAP 0
@@ -620,14 +641,16 @@ int insr_svd_energy_bwd(const float* J, long n, int d, float ratio_arap, float r
 #define INSR_EL_CONSTRAINT_RIGHT 5
 #define INSR_EL_COLLISION 6
 #define INSR_EL_SPHERE 7
-#define INSR_EL_TERMS 8
+#define INSR_EL_NEOHOOKEAN 8
+#define INSR_EL_STVK 9
+#define INSR_EL_TERMS 10
 typedef struct InsrElastic {
   int d;               /* 2 or 3 */
   int n_order;         /* terms in order[] */
   long n;              /* interior rows */
   long rows;           /* rows of f / J / gf / gJ */
   const float* f;      /* (rows, d) trainable field */
-  const float* J;      /* (rows, d, d) its Jacobian (no identity); NULL without ARAP / VOLUME */
+  const float* J;      /* (rows, d, d) its Jacobian (no identity); NULL without a term that reads it */
   const float* x;      /* (n, d) interior points */
   const float* f_prev; /* (n, d) */
   const float* f_pp;   /* (n, d) */
@@ -644,6 +667,7 @@ typedef struct InsrElastic {
   float* terms;        /* INSR_EL_TERMS floats, or NULL */
   float* gf;
   float* gJ;
+  float mu, lam;       /* Lame parameters of NEOHOOKEAN / STVK */
 } InsrElastic;
 long insr_elastic_work_floats(void);
 int insr_elastic_energy(const InsrElastic* e, float* work, void* stream);

@@ -166,6 +166,8 @@ SIGNATURES = {
     "insr_svd_energy_work_floats": (_L, []),
     "insr_svd_energy_fwd": (_I, [_P, _L, _I, _F, _F, _P, _P, _P]),
     "insr_svd_energy_bwd": (_I, [_P, _L, _I, _F, _F, _P, _P, _P]),
+    "insr_hyperelastic_fwd": (_I, [_P, _L, _I, _I, _F, _F, _P, _P, _P]),
+    "insr_hyperelastic_bwd": (_I, [_P, _L, _I, _I, _F, _F, _P, _P, _P]),
     "insr_elastic_work_floats": (_L, []),
     "insr_elastic_energy": (_I, [_P, _P, _P]),
     "insr_sq_loss_fwd": (_I, [_I, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P, _P, _P]),
@@ -274,9 +276,10 @@ class Mesh(ctypes.Structure):
     _fields_ = [("cdf", _P), ("corners", _P), ("k", _L), ("nc", _I), ("dim", _I)]
 
 
-EL_TERMS = 8  # INSR_EL_TERMS; term ids INSR_EL_ARAP ... INSR_EL_SPHERE
+EL_TERMS = 10  # INSR_EL_TERMS; term ids INSR_EL_ARAP ... INSR_EL_STVK
 EL_IDS = {"arap": 0, "volume": 1, "kinematics": 2, "external": 3, "constraint": 4, "constraint_right": 5,
-          "collision": 6, "collision_sphere": 7}
+          "collision": 6, "collision_sphere": 7, "neohookean": 8, "stvk": 9}
+EL_MATERIALS = {"neohookean": 0, "stvk": 1}  # `material` of insr_hyperelastic_fwd / bwd
 
 
 class Elastic(ctypes.Structure):
@@ -285,7 +288,7 @@ class Elastic(ctypes.Structure):
                 ("f_prev", _P), ("f_pp", _P), ("dt", _F), ("ratio", _F * EL_TERMS), ("ext", _F * 3),
                 ("target", _F * 3), ("plane_height", _F), ("center", _F * 3), ("radius", _F),
                 ("row_l", _L), ("n_l", _L), ("row_r", _L), ("n_r", _L), ("order", _I * EL_TERMS),
-                ("out", _P), ("terms", _P), ("gf", _P), ("gJ", _P)]
+                ("out", _P), ("terms", _P), ("gf", _P), ("gJ", _P), ("mu", _F), ("lam", _F)]
 
 
 class NativeUnavailable(RuntimeError):

@@ -569,7 +569,77 @@ def svd_energy(J, ratio_arap=1.0, ratio_volume=0.0, count=None):
     return _SvdEnergy.apply(_prep(J), ratio_arap, ratio_volume, n)
 
 
+def _check_material(material, mu, lam):
+    """The Lame parameters a hyperelastic material needs (what the library would refuse with INSR_EINVAL)."""
+    import math
+    if material not in nat.EL_MATERIALS:
+        raise ValueError(f"unknown material {material!r} (one of {sorted(nat.EL_MATERIALS)})")
+    if mu is None or lam is None:
+        raise ValueError(f"{material}: the Lame parameters mu and lam are required")
+    mu, lam = float(mu), float(lam)
+    if not (math.isfinite(mu) and math.isfinite(lam)):
+        raise ValueError(f"{material}: mu = {mu}, lam = {lam} must be finite")
+    if material == "neohookean" and not (lam > 0.0 and mu >= 0.0):
+        raise ValueError(f"neohookean: needs lam > 0 and mu >= 0 (alpha = 1 + (mu / lam) d / (d + 1)), "
+                         f"got mu = {mu}, lam = {lam}")
+    return mu, lam
+
+
+class _HyperelasticEnergy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, J, material, mu, lam, n):
+        lib = nat.lib()
+        dev = J.device
+        key = _stream_key(dev)
+        if key not in _SVD_WORK:  # the SVD pair's partials buffer (same reduction scheme)
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("hyperelastic-energy workspace must be created before graph capture "
+                                   "(run one eager call)")
+            _SVD_WORK[key] = torch.empty(lib.insr_svd_energy_work_floats(), device=dev, dtype=torch.float32)
+        out = torch.empty((), device=dev, dtype=torch.float32)
+        rc = lib.insr_hyperelastic_fwd(nat.ptr(J), n, J.shape[-1], material, mu, lam, nat.ptr(out),
+                                       nat.ptr(_SVD_WORK[key]), nat.stream_of(dev))
+        nat.check(rc, "insr_hyperelastic_fwd")
+        ctx.save_for_backward(J)
+        ctx.args = (material, mu, lam, n)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        (J,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        material, mu, lam, n = ctx.args
+        gJ = torch.empty_like(J) if n == J.shape[0] else torch.zeros_like(J)
+        g = gout.reshape(1) if gout.is_contiguous() else gout.contiguous().reshape(1)
+        rc = nat.lib().insr_hyperelastic_bwd(nat.ptr(J), n, J.shape[-1], material, mu, lam, nat.ptr(g), nat.ptr(gJ),
+                                             nat.stream_of(J.device))
+        nat.check(rc, "insr_hyperelastic_bwd")
+        return gJ, None, None, None, None
+
+
+def hyperelastic_energy(J, material, mu, lam, count=None):
+    """sum over points of psi(F), F = J[n] the deformation gradient dq/dx itself (d x d, d = 2 or 3), with
+    the Lame parameters mu, lam -- one launch forward, one backward (the first Piola stress dpsi/dF in
+    closed form; no SVD, smooth through repeated singular values and inversion):
+      'neohookean'  stable Neo-Hookean (Smith et al. 2018) shifted to zero at rest, I_C = |F|^2, det = det F:
+                    psi = mu/2 (I_C - d) + lam/2 (det - alpha)^2 - mu/2 log(I_C + 1) - psi_0,
+                    alpha = 1 + (mu / lam) d / (d + 1), psi_0 = lam/2 (1 - alpha)^2 - mu/2 log(d + 1)
+                    (lam > 0, mu >= 0; zero stress at F = I)
+      'stvk'        St. Venant-Kirchhoff, E = (F^T F - I) / 2: psi = mu |E|^2 + lam/2 tr(E)^2
+    Evaluated from F - I, so the value and the gradient are exactly 0 at rest.  count: only the first
+    `count` blocks (the other blocks get zero gradient), as svd_energy."""
+    if J.dim() != 3 or J.shape[-1] != J.shape[-2] or J.shape[-1] not in (2, 3):
+        raise ValueError(f"hyperelastic_energy: expected (N, d, d) with d in (2, 3), got {tuple(J.shape)}")
+    mu, lam = _check_material(material, mu, lam)
+    n = J.shape[0] if count is None else int(count)
+    if n > J.shape[0] or n < 0:
+        raise ValueError(f"hyperelastic_energy: count {n} > {J.shape[0]} blocks")
+    return _HyperelasticEnergy.apply(_prep(J), nat.EL_MATERIALS[material], mu, lam, n)
+
+
 _EL_WORK = {}  # (device index, stream handle) -> per-term partials + ticket of insr_elastic_energy
+_J_TERMS = ("arap", "volume", "neohookean", "stvk")  # the terms of insr_elastic_energy that read the Jacobian
 
 
 class _ElasticEnergy(torch.autograd.Function):
@@ -591,15 +661,15 @@ class _ElasticEnergy(torch.autograd.Function):
         terms = torch.empty(nat.EL_TERMS, device=dev, dtype=torch.float32)
         need_f, need_J = ctx.needs_input_grad[0], J is not None and ctx.needs_input_grad[1]
         gf = torch.empty_like(f) if need_f else None
-        # the kernel writes dE/dJ only when an SVD term (arap / volume) has a nonzero ratio
-        # (svd_energy.hip); otherwise the gradient w.r.t. J is exactly zero
-        svd_on = any(spec["ratio"].get(nat.EL_IDS[t], 0.0) != 0.0 for t in ("arap", "volume"))
-        gJ = (torch.empty_like(J) if svd_on else torch.zeros_like(J)) if need_J else None
+        # the kernel writes dE/dJ only when a term that reads J (arap / volume / neohookean / stvk) has
+        # a nonzero ratio (svd_energy.hip); otherwise the gradient w.r.t. J is exactly zero
+        j_on = any(spec["ratio"].get(nat.EL_IDS[t], 0.0) != 0.0 for t in _J_TERMS)
+        gJ = (torch.empty_like(J) if j_on else torch.zeros_like(J)) if need_J else None
         e = nat.Elastic()
         d = f.shape[1]
         e.d, e.n, e.rows = d, spec["n"], f.shape[0]
         e.f, e.J, e.x, e.f_prev, e.f_pp = nat.ptr(f), nat.ptr(J), nat.ptr(x), nat.ptr(f_prev), nat.ptr(f_pp)
-        e.dt = spec["dt"]
+        e.dt, e.mu, e.lam = spec["dt"], spec["mu"], spec["lam"]
         for t, r in spec["ratio"].items():
             e.ratio[t] = r
         for k in range(d):
@@ -630,17 +700,25 @@ class _ElasticEnergy(torch.autograd.Function):
 
 def elastic_energy(f, J, x, f_prev, f_pp, *, n, dt, energy, ratios, ext=(0.0, 0.0, 0.0), external_on=True,
                    rows_l=(0, 0), rows_r=(0, 0), target=(0.0, 0.0, 0.0), plane_height=0.0, center=(0.0, 0.0, 0.0),
-                   radius=0.0):
+                   radius=0.0, mu=None, lam=None):
     """The elastodynamics energy of elasticity/model.py:131-186 in ONE launch (insr_elastic_energy).
 
     f: (rows, d) trainable field values of one merged jet launch -- rows [0, n) at the interior
     points x, rows_l = (first row, count) / rows_r the fixed points of the positional
-    constraints; J: (rows, d, d) the field's Jacobian df/dx (None without arap / volume);
-    f_prev, f_pp: the frozen fields at x.  energy: cfg.energy (terms are added in that order);
-    ratios: {term: ratio}.  Returns (total, terms) -- total differentiable w.r.t. f and J,
-    terms (8 floats, non-differentiable) the per-term values (index INSR_EL_*, base._native.EL_IDS)."""
+    constraints; J: (rows, d, d) the field's Jacobian df/dx (None without arap / volume /
+    neohookean / stvk); f_prev, f_pp: the frozen fields at x.  energy: cfg.energy (terms are added
+    in that order); ratios: {term: ratio}.  'neohookean' (stable Neo-Hookean) and 'stvk' are the
+    hyperelastic materials sum psi(J + I) with the Lame parameters mu, lam (hyperelastic_energy has
+    the formulas); their weight is 1 (a ratios entry of 0 switches one off).  Returns (total, terms)
+    -- total differentiable w.r.t. f and J, terms (base._native.EL_TERMS = 10 floats,
+    non-differentiable) the per-term values (index INSR_EL_*, base._native.EL_IDS)."""
     ids = nat.EL_IDS
     order, ratio = [], {}
+    for term in energy:
+        if term in nat.EL_MATERIALS:
+            _check_material(term, mu, lam)
+            if J is None:
+                raise ValueError(f"elastic_energy: {term!r} reads the Jacobian J")
     if "constraint_right" in energy and "constraint_right_compress" in energy:
         # the reference adds two terms with opposite targets; the fused launch has one slot
         raise _unsupported("constraint_right and constraint_right_compress together are not fused")
@@ -654,8 +732,12 @@ def elastic_energy(f, J, x, f_prev, f_pp, *, n, dt, energy, ratios, ext=(0.0, 0.
         if term == "external" and not external_on:
             continue
         order.append(t)
-        ratio[t] = 1.0 if term == "external" else float(ratios[term])
+        if term in nat.EL_MATERIALS:  # on / off
+            ratio[t] = 1.0 if float(ratios.get(term, 1.0)) != 0.0 else 0.0
+        else:
+            ratio[t] = 1.0 if term == "external" else float(ratios[term])
     spec = {"n": int(n), "dt": float(dt), "ratio": ratio, "order": order, "ext": [float(v) for v in ext],
+            "mu": 0.0 if mu is None else float(mu), "lam": 0.0 if lam is None else float(lam),
             "target": [float(v) for v in target], "center": [float(v) for v in center],
             "plane_height": float(plane_height), "radius": float(radius),
             "rows_l": tuple(int(v) for v in rows_l), "rows_r": tuple(int(v) for v in rows_r)}

@@ -945,7 +945,7 @@ using namespace insr;
 
 extern "C" {
 
-int insr_version(void) { return 300; }
+int insr_version(void) { return 400; }
 
 long insr_siren_param_count(int din, int dout, int L, int W) {
   return (long)W * din + W + (long)L * ((long)W * W + W) + (long)dout * W + dout;

@@ -17,6 +17,7 @@
 //        convergence: fp32-exact for these 3x3 blocks); no squaring of J^T J, so
 //        small singular values keep their relative accuracy.
 #include "jet_common.hpp"
+#include "hyperelastic.hpp"
 
 namespace insr {
 
@@ -225,11 +226,67 @@ __global__ __launch_bounds__(kSvdThreads) void svd_energy_bwd_kernel(const float
   }
 }
 
+// The stand-alone hyperelastic energy (insr_hyperelastic_fwd/bwd): J holds F = dq/dx itself, as in
+// the SVD pair; the identity is subtracted in registers.  psi of one point, w * dpsi/dF added to P.
+template <int D>
+__device__ __forceinline__ float hyper_point(const float* F, int material, float mu, float lam, float w,
+                                             float (&P)[D * D]) {
+  float G[D * D];
+#pragma unroll
+  for (int k = 0; k < D * D; ++k) G[k] = F[k] - ((k % (D + 1) == 0) ? 1.f : 0.f);
+  return material == 0 ? neohookean_point<D>(G, mu, lam, w, P) : stvk_point<D>(G, mu, lam, w, P);
+}
+
+__global__ __launch_bounds__(kSvdThreads) void hyperelastic_fwd_kernel(const float* __restrict__ J, long n, int d,
+                                                                       int material, float mu, float lam,
+                                                                       float* __restrict__ out) {
+  __shared__ float red[kSvdThreads / 64];
+  float acc = 0.f;
+  for (long i = (long)blockIdx.x * kSvdThreads + threadIdx.x; i < n; i += (long)gridDim.x * kSvdThreads) {
+    if (d == 2) {
+      float P[4] = {0.f, 0.f, 0.f, 0.f};
+      acc += hyper_point<2>(J + i * 4, material, mu, lam, 0.f, P);
+    } else {
+      float P[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      acc += hyper_point<3>(J + i * 9, material, mu, lam, 0.f, P);
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) red[w] = acc;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  float part = 0.f;
+  for (int k = 0; k < kSvdThreads / 64; ++k) part += red[k];
+  out[blockIdx.x] = part;
+}
+
+__global__ __launch_bounds__(kSvdThreads) void hyperelastic_bwd_kernel(const float* __restrict__ J, long n, int d,
+                                                                       int material, float mu, float lam,
+                                                                       const float* __restrict__ gout,
+                                                                       float* __restrict__ gJ) {
+  const float go = gout[0];
+  for (long i = (long)blockIdx.x * kSvdThreads + threadIdx.x; i < n; i += (long)gridDim.x * kSvdThreads) {
+    if (d == 2) {
+      float P[4] = {0.f, 0.f, 0.f, 0.f};
+      hyper_point<2>(J + i * 4, material, mu, lam, go, P);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) gJ[i * 4 + k] = P[k];
+    } else {
+      float P[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      hyper_point<3>(J + i * 9, material, mu, lam, go, P);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) gJ[i * 9 + k] = P[k];
+    }
+  }
+}
+
 
 // ---------------------------------------------------------------------------------------
 // The whole elastodynamics energy of one iteration (insr_elastic_energy): one thread per row
 // of the trainable field's merged jet; interior rows (< n) carry ARAP / volume (the SVD of
-// dq/dx = J + I), kinematics, external force and collision terms, the constraint rows their
+// dq/dx = J + I), the hyperelastic materials on the same J (stable Neo-Hookean / StVK,
+// hyperelastic.hpp: no SVD), kinematics, external force and collision terms, the constraint rows their
 // positional terms.  Each term's raw sum is reduced separately (deterministic, block order,
 // last block combines), scaled like the reference and added in cfg.energy order; the
 // gradient for a unit seed is written in the same pass.
@@ -237,21 +294,49 @@ __global__ __launch_bounds__(kSvdThreads) void svd_energy_bwd_kernel(const float
 constexpr int kElThreads = 256;
 constexpr int kElMaxBlocks = 1024;
 // reduced sums: the INSR_EL_TERMS terms' raw sums, then the 3-D sphere's second factor
-// (sum qdot . dir over the colliding rows; the term's own slot holds sum |q - c|)
+// (sum qdot . dir over the colliding rows; the term's own slot holds sum |q - c|).  The kernel instance
+// without materials drops their two slots (its kAcc / kSphB); the workspace is sized for the full layout
 constexpr int kElSphereB = INSR_EL_TERMS;
+static_assert(kElSphereB == INSR_EL_STVK + 1, "the materials' slots are the last two terms");
 constexpr int kElAcc = INSR_EL_TERMS + 1;
 // work: [kElAcc][kElMaxBlocks] block partials, the ticket, then the 3-D sphere's two sums for
 // the gradient pass (elastic_sphere3_grad_kernel)
 constexpr long kElTicket = (long)kElAcc * kElMaxBlocks;
 
+// row r's material terms: psi into the two raw sums, the first Piola stress into (or, after the SVD
+// terms, onto) gJ's row
+template <int D>
+__device__ __forceinline__ void acc_materials(const InsrElastic& E, long r, bool nh, bool sk, bool add, float& a_nh,
+                                              float& a_sk) {
+  float G[D * D], gj[D * D];
+#pragma unroll
+  for (int k = 0; k < D * D; ++k) {
+    G[k] = E.J[r * (D * D) + k];
+    gj[k] = 0.f;
+  }
+  if (nh) a_nh += neohookean_point<D>(G, E.mu, E.lam, 1.f, gj);
+  if (sk) a_sk += stvk_point<D>(G, E.mu, E.lam, 1.f, gj);
+  if (!E.gJ) return;
+#pragma unroll
+  for (int k = 0; k < D * D; ++k) E.gJ[r * (D * D) + k] = add ? E.gJ[r * (D * D) + k] + gj[k] : gj[k];
+}
+
+// MAT: the launch has a material on.  Without one the kernel is instantiated without the materials' code and
+// their two reduction slots (kAcc = 9 sums, as before the materials existed): the existing configurations run
+// the kernel they ran, register for register.
+template <bool MAT>
 __global__ __launch_bounds__(kElThreads) void elastic_energy_kernel(const InsrElastic E, float* __restrict__ work) {
-  __shared__ float red[kElAcc][kElThreads / 64];
+  constexpr int kAcc = MAT ? kElAcc : kElAcc - 2;  // reduced sums of this instance
+  constexpr int kSphB = kAcc - 1;                  // the 3-D sphere's second factor: the last of them
+  __shared__ float red[kAcc][kElThreads / 64];
   const int d = E.d;
   const float dt = E.dt;
   const bool svd = E.ratio[INSR_EL_ARAP] != 0.f || E.ratio[INSR_EL_VOLUME] != 0.f;
-  float acc[kElAcc];
+  const bool nh = MAT && E.ratio[INSR_EL_NEOHOOKEAN] != 0.f, sk = MAT && E.ratio[INSR_EL_STVK] != 0.f;
+  const bool jterm = svd || nh || sk;  // gJ is written, zeros on the constraint rows included
+  float acc[kAcc];
 #pragma unroll
-  for (int t = 0; t < kElAcc; ++t) acc[t] = 0.f;
+  for (int t = 0; t < kAcc; ++t) acc[t] = 0.f;
   for (long r = (long)blockIdx.x * kElThreads + threadIdx.x; r < E.rows; r += (long)gridDim.x * kElThreads) {
     float gf[3] = {0.f, 0.f, 0.f};
     if (r < E.n) {
@@ -294,7 +379,7 @@ __global__ __launch_bounds__(kElThreads) void elastic_energy_kernel(const InsrEl
         if (d == 3) {  // the two factors of the 3-D product; the gradient pass follows the totals
           if (dist < E.radius) {
             acc[INSR_EL_SPHERE] += dist;
-            acc[kElSphereB] += qd[0] * (vec[0] / dist) + qd[1] * (vec[1] / dist) + qd[2] * (vec[2] / dist);
+            acc[kSphB] += qd[0] * (vec[0] / dist) + qd[1] * (vec[1] / dist) + qd[2] * (vec[2] / dist);
           }
         } else if (dist < E.radius) {  // 2-D: -dt sum qdot . rc dist dir
           const float rd = E.ratio[INSR_EL_SPHERE] * dist;
@@ -333,6 +418,15 @@ __global__ __launch_bounds__(kElThreads) void elastic_energy_kernel(const InsrEl
           if (E.gJ) grad3(Jq, B, V, s, 1.f, de, E.gJ + r * 9);
         }
       }
+      // the hyperelastic materials, from J itself (hyperelastic.hpp).  A block of its own that reads J
+      // again and adds to what the SVD terms wrote for this row: nothing of it is live across the Jacobi
+      // sweeps, so a launch without a material keeps the registers it had
+      if constexpr (MAT) {
+        if (d == 2)
+          acc_materials<2>(E, r, nh, sk, svd, acc[INSR_EL_NEOHOOKEAN], acc[INSR_EL_STVK]);
+        else
+          acc_materials<3>(E, r, nh, sk, svd, acc[INSR_EL_NEOHOOKEAN], acc[INSR_EL_STVK]);
+      }
     } else {
       if (r >= E.row_l && r < E.row_l + E.n_l) {  // rc sum |f(x_l)|^2
 #pragma unroll
@@ -352,7 +446,7 @@ __global__ __launch_bounds__(kElThreads) void elastic_energy_kernel(const InsrEl
           gf[k] += E.ratio[INSR_EL_CONSTRAINT_RIGHT] * (2.f * v);
         }
       }
-      if (E.gJ && svd)
+      if (E.gJ && jterm)
         for (int k = 0; k < d * d; ++k) E.gJ[r * d * d + k] = 0.f;
     }
     if (E.gf)
@@ -362,21 +456,21 @@ __global__ __launch_bounds__(kElThreads) void elastic_energy_kernel(const InsrEl
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
-  for (int t = 0; t < kElAcc; ++t) {
+  for (int t = 0; t < kAcc; ++t) {
     float v = acc[t];
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     if (lane == 0) red[t][w] = v;
   }
-  __shared__ float tot[kElAcc];
+  __shared__ float tot[kAcc];
   __shared__ int last;
   __syncthreads();
-  if (threadIdx.x < kElAcc) {  // the block's partial of sum t (waves in order)
+  if (threadIdx.x < kAcc) {  // the block's partial of sum t (waves in order)
     const int t = threadIdx.x;
     float part = 0.f;
 #pragma unroll
     for (int k = 0; k < kElThreads / 64; ++k) part += red[t][k];
     tot[t] = part;
-    if (gridDim.x > 1)  // sc1 partial store; the wait below covers all eight lanes' stores
+    if (gridDim.x > 1)  // sc1 partial store; the wait below covers all kAcc lanes' stores
       __hip_atomic_store(work + t * kElMaxBlocks + blockIdx.x, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   if (threadIdx.x == 0) {
@@ -394,15 +488,15 @@ __global__ __launch_bounds__(kElThreads) void elastic_energy_kernel(const InsrEl
     // the last block: wave w sums w, w + 4, w + 8 over every block's partial, lanes load in
     // parallel (lane l: blocks l, l + 64, ...), fixed butterfly -- deterministic
 #pragma unroll
-    for (int h = 0; h < (kElAcc + 3) / 4; ++h) {
+    for (int h = 0; h < (kAcc + 3) / 4; ++h) {
       const int t = w + 4 * h;
       float v = 0.f;
-      if (t < kElAcc)
+      if (t < kAcc)
         for (int q = lane; q < (int)gridDim.x; q += 64)
           v += __hip_atomic_load(work + t * kElMaxBlocks + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
       __syncthreads();
-      if (lane == 0 && t < kElAcc) tot[t] = v;
+      if (lane == 0 && t < kAcc) tot[t] = v;
     }
     __syncthreads();
   }
@@ -413,8 +507,10 @@ __global__ __launch_bounds__(kElThreads) void elastic_energy_kernel(const InsrEl
 #pragma unroll
   for (int t = 0; t < INSR_EL_TERMS; ++t) {
     const float scale = (t == INSR_EL_EXTERNAL || t == INSR_EL_COLLISION || t == INSR_EL_SPHERE) ? -dt : E.ratio[t];
-    et[t] = scale * tot[t];
-    if (t == INSR_EL_SPHERE && d == 3) et[t] = -dt * (E.ratio[t] * tot[t]) * tot[kElSphereB];
+    const float raw = t < kSphB ? tot[t < kSphB ? t : 0] : 0.f;  // (no material slots in the instance without them)
+    et[t] = scale * raw;
+    if (t == INSR_EL_NEOHOOKEAN || t == INSR_EL_STVK) et[t] = raw;  // sum psi: the ratio is on / off
+    if (t == INSR_EL_SPHERE && d == 3) et[t] = -dt * (E.ratio[t] * tot[t]) * tot[kSphB];
     if (E.terms) E.terms[t] = et[t];
   }
   float loss = 0.f;
@@ -427,7 +523,7 @@ __global__ __launch_bounds__(kElThreads) void elastic_energy_kernel(const InsrEl
   E.out[0] = loss;
   if (d == 3 && E.ratio[INSR_EL_SPHERE] != 0.f) {  // the two sums, for the gradient pass
     work[kElTicket + 1] = tot[INSR_EL_SPHERE];
-    work[kElTicket + 2] = tot[kElSphereB];
+    work[kElTicket + 2] = tot[kSphB];
   }
   if (gridDim.x > 1) atomicExch(reinterpret_cast<unsigned*>(work + kElTicket), 0u);
 }
@@ -498,6 +594,37 @@ int insr_svd_energy_bwd(const float* J, long n, int d, float ratio_arap, float r
 }
 
 
+// a material's Lame parameters: stable Neo-Hookean divides by lam (alpha = 1 + (mu / lam) d / (d + 1))
+static bool material_ok(int material, float mu, float lam) {
+  if (!isfinite(mu) || !isfinite(lam)) return false;
+  return material == 0 ? (lam > 0.f && mu >= 0.f) : material == 1;
+}
+
+int insr_hyperelastic_fwd(const float* J, long n, int d, int material, float mu, float lam, float* out, float* work,
+                          void* stream) {
+  if (!J || !out || n < 0 || (d != 2 && d != 3) || !material_ok(material, mu, lam)) return INSR_EINVAL;
+  long nb = (n + 4 * kSvdThreads - 1) / (4 * kSvdThreads);  // the SVD pair's shape: ~4 points per thread
+  if (nb < 1) nb = 1;
+  if (nb > kSvdMaxBlocks) nb = kSvdMaxBlocks;
+  if (nb > 1 && !work) return INSR_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(hyperelastic_fwd_kernel, dim3((unsigned)nb), dim3(kSvdThreads), 0, st, J, n, d, material, mu, lam,
+                     nb > 1 ? work : out);
+  if (nb > 1) hipLaunchKernelGGL(svd_combine_kernel, dim3(1), dim3(64), 0, st, work, (int)nb, out);
+  return (int)hipGetLastError();
+}
+
+int insr_hyperelastic_bwd(const float* J, long n, int d, int material, float mu, float lam, const float* gout,
+                          float* gJ, void* stream) {
+  if (!J || !gout || !gJ || n < 0 || (d != 2 && d != 3) || !material_ok(material, mu, lam)) return INSR_EINVAL;
+  if (n == 0) return 0;
+  long nb = (n + kSvdThreads - 1) / kSvdThreads;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(hyperelastic_bwd_kernel, dim3((unsigned)nb), dim3(kSvdThreads), 0, (hipStream_t)stream, J, n, d,
+                     material, mu, lam, gout, gJ);
+  return (int)hipGetLastError();
+}
+
 long insr_elastic_work_floats(void) { return kElTicket + 4; }
 
 int insr_elastic_energy(const InsrElastic* e, float* work, void* stream) {
@@ -506,6 +633,9 @@ int insr_elastic_energy(const InsrElastic* e, float* work, void* stream) {
   if (e->rows > e->n && !e->f) return INSR_EINVAL;
   const bool svd = e->ratio[INSR_EL_ARAP] != 0.f || e->ratio[INSR_EL_VOLUME] != 0.f;
   if (svd && e->n > 0 && !e->J) return INSR_EINVAL;
+  const bool nh = e->ratio[INSR_EL_NEOHOOKEAN] != 0.f, sk = e->ratio[INSR_EL_STVK] != 0.f;
+  if ((nh || sk) && !e->J) return INSR_EINVAL;
+  if ((nh && !material_ok(0, e->mu, e->lam)) || (sk && !material_ok(1, e->mu, e->lam))) return INSR_EINVAL;
   if (!(e->dt > 0.f) || e->n_order < 0 || e->n_order > INSR_EL_TERMS) return INSR_EINVAL;
   const bool sphere3 = e->ratio[INSR_EL_SPHERE] != 0.f && e->d == 3;  // 3-D: a product of two sums
   for (int k = 0; k < e->n_order; ++k)
@@ -519,7 +649,12 @@ int insr_elastic_energy(const InsrElastic* e, float* work, void* stream) {
   if (nb < 1) nb = 1;
   if (nb > kElMaxBlocks) nb = kElMaxBlocks;
   if ((nb > 1 || sphere3) && !work) return INSR_EINVAL;
-  hipLaunchKernelGGL(elastic_energy_kernel, dim3((unsigned)nb), dim3(kElThreads), 0, (hipStream_t)stream, *e, work);
+  if (nh || sk)
+    hipLaunchKernelGGL(elastic_energy_kernel<true>, dim3((unsigned)nb), dim3(kElThreads), 0, (hipStream_t)stream, *e,
+                       work);
+  else
+    hipLaunchKernelGGL(elastic_energy_kernel<false>, dim3((unsigned)nb), dim3(kElThreads), 0, (hipStream_t)stream, *e,
+                       work);
   if (sphere3 && e->gf && e->n > 0) {
     long ng = (e->n + kElThreads - 1) / kElThreads;
     if (ng > kElMaxBlocks) ng = kElMaxBlocks;

@@ -29,6 +29,8 @@ EXEC = dict(insr_precision=None, insr_sync_every=1, insr_graph=False, insr_graph
             insr_seed_in_bwd=True,  # opted-in phase bodies' loss groups ride in the reverse jets (base/losses.py)
             insr_mesh_batch=False,  # mesh scenes: one device sampler launch into a persistent batch (opt-in:
                                     # the device Philox stream, not torch's generator; pde/elasticity.py _mesh_batch)
+            # Lame parameters of the hyperelastic energy terms 'neohookean' / 'stvk' (pde/elasticity.py)
+            insr_lame_mu=None, insr_lame_lambda=None,
             insr_fuse_forwards=os.environ.get("INSR_FUSE_FORWARDS", "1") != "0")
 
 

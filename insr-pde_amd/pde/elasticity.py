@@ -5,6 +5,9 @@ elasticity/losses.py:6-39), on the insr-pde_amd `base` API.
 Energy terms (all SUMS over collocation points, as in the reference):
   arap        r_a  sum (sigma_i - 1)^2         sigma = singular values of dq/dx
   volume      r_v  sum (prod sigma_i - 1)^2
+  neohookean  sum psi(dq/dx), stable Neo-Hookean with the Lame parameters cfg.insr_lame_mu / insr_lame_lambda
+  stvk        sum psi(dq/dx), St. Venant-Kirchhoff with the same parameters (both beyond the reference:
+              base.hyperelastic_energy has the formulas; per-point sums, so strong-scaling shards add up)
   kinematics  r_k  sum |qdot - qdot_prev|^2     qdot = (q - q_prev)/dt
   external    -dt  sum qdot . f_ext             (first T_ext timesteps)
   constraint(_right[_compress]) r_c sum |f(x_fixed) - target|^2
@@ -53,6 +56,8 @@ class ElasticityModel(BaseModel):
         self.ratio_arap, self.ratio_volume = cfg.ratio_arap, cfg.ratio_volume
         self.ratio_kinematics, self.ratio_constraint = cfg.ratio_kinematics, cfg.ratio_constraint
         self.ratio_collide = cfg.ratio_collide
+        self.lame_mu = getattr(cfg, "insr_lame_mu", None)
+        self.lame_lambda = getattr(cfg, "insr_lame_lambda", None)
         self.external_force_timesteps = cfg.external_force_timesteps
         self.plane_height = cfg.plane_height
         self.circle_radius = cfg.collide_circle_radius
@@ -377,7 +382,7 @@ class ElasticityModel(BaseModel):
         # every term in ONE launch with its unit-seed gradient (base.elastic_energy): the
         # singular values of dq/dx = J + I, kinematics, external force, collisions and the
         # positional constraints; J is the Jacobian jet of the same field launch
-        J = jacobian_only(fa, xa) if ('arap' in self.energy or 'volume' in self.energy) else None
+        J = jacobian_only(fa, xa) if any(t in self.energy for t in ('arap', 'volume', 'neohookean', 'stvk')) else None
         sign = -1.0 if 'constraint_right_compress' in self.energy else 1.0
         ratios = {'arap': self.ratio_arap, 'volume': self.ratio_volume, 'kinematics': self.ratio_kinematics,
                   'constraint': self.ratio_constraint, 'constraint_right': self.ratio_constraint,
@@ -388,7 +393,7 @@ class ElasticityModel(BaseModel):
             ext=self._host_vec('external_force'), external_on=self.timestep <= self.external_force_timesteps,
             rows_l=(row_l, fixed_l.shape[0] if use_l else 0), rows_r=(row_r, fixed_r.shape[0] if use_r else 0),
             target=[sign * v for v in self._host_vec('constraint_offset_right')], plane_height=self.plane_height,
-            center=self._host_vec('circle_center'), radius=self.circle_radius)
+            center=self._host_vec('circle_center'), radius=self.circle_radius, mu=self.lame_mu, lam=self.lame_lambda)
         return total
 
     def _host_vec(self, name):
